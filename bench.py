@@ -45,6 +45,13 @@ the codec the way N = 1 does. --comm / --scaling choose the headline explicitly.
 
 value = (encoded bytes + decoded bytes) over all ranks / max-over-ranks step time, in GB/s (1e9).
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) does what that number needs and no more: setup,
+warmup, the K timed steps, their verification, the one JSON line. ``--full`` adds everything this text
+describes that is timed after the headline: value_by_comm / value_strong (N > 1 or --force-pg), the e2e
+block behind vs_baseline, and the other BASELINE configs (--configs). ``--dump-outputs DIR`` writes the
+last timed step's parity and decoded rows (a fixed sample of their columns) as DIR/*.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared array for array.
+
 Failure isolation (N > 1). The headline is timed, verified and reduced FIRST (step_ms_by_rank shows
 every rank's own step time, so a straggler is visible). Only then do the comparison modes run, one
 at a time (e2e, none, owners, strong, root: least collective risk first), each in its own try under
@@ -79,6 +86,21 @@ from __future__ import annotations
 import os
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this driver (RCCL peers)
+
+
+def _tree_writable(root: str) -> bool:
+    """Whether this user could rebuild the native modules in place (make writes under build/)."""
+    for p in (os.path.join(root, "build", ".lock"), os.path.join(root, "build"), root):
+        if os.path.exists(p):
+            return os.access(p, os.W_OK)
+    return False
+
+
+# The benchmark runs the modules as build() left them. In a tree this user cannot write (built by
+# another account, a read-only mount) there is nothing the loader's staleness check could rebuild,
+# so it is skipped: the modules are imported as they are, and a missing one is still an error.
+if not _tree_writable(os.path.dirname(os.path.abspath(__file__))):
+    os.environ.setdefault("GPURS_NO_BUILD", "1")
 
 import argparse  # noqa: E402
 import datetime  # noqa: E402
@@ -132,6 +154,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=None, help="ranks / GPUs (default: WORLD_SIZE, else 1)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also time everything else: the pinned host->device->host e2e "
+                         "pipeline, the other --comm / --scaling modes (with a process group) and the --configs "
+                         "presets. Without it a run sets up, warms up, times --steps steps and prints the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed, parity.npy [n-k, S] and "
+                         "decoded.npy [k, S] (float32 byte values; S: every column, or a fixed seeded sample of "
+                         "them when the rows are longer), into DIR (N > 1: <name>.rank<r>.npy per rank)")
     ap.add_argument("--min-warmup-ms", type=float, default=None,
                     help="before the --warmup steps, run local steps (no collectives) until this many ms have "
                          "passed, so the timed steps start at sustained clocks (default 250 on cuda, 0 on cpu; "
@@ -187,7 +217,7 @@ def parse(argv=None):
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the C++ CPU codec over gloo (launcher / communication plumbing on a host)")
     ap.add_argument("--configs", default=None,
-                    help="N = 1: after the headline, time these presets (comma list) each in a fresh child "
+                    help="--full, N = 1: after the headline, time these presets (comma list) each in a fresh child "
                          "process and embed their records under configs (default on cuda with the k10n14 "
                          f"headline: {','.join(CONFIG_PRESETS)}; 'none': off)")
     ap.add_argument("--config-steps", type=int, default=20, help="timed steps of each --configs child")
@@ -268,6 +298,34 @@ def _oracle_gemm(e_mat: np.ndarray, x: np.ndarray, wide: bool) -> np.ndarray:
         return gf.GF256.gemm(e_mat, x)
     out = gf.field(16).gemm(e_mat, np.ascontiguousarray(x).view("<u2"))
     return np.ascontiguousarray(out.astype("<u2")).view(np.uint8)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes over all arrays (the whole output is 1.4 GiB per GPU)
+
+
+def _dump_columns(C: int, count: int, block: int = 256) -> np.ndarray:
+    """The columns --dump-outputs keeps of a row of C bytes: all of them when count >= C, else the
+    first and the last `block` columns (the ragged tail) and seeded random aligned blocks between them
+    — the same columns in every run with the same C and count."""
+    if count >= C:
+        return np.arange(C, dtype=np.int64)
+    rng = np.random.default_rng(20260)
+    starts = rng.choice(C // block, size=max(1, count // block - 2), replace=False).astype(np.int64) * block
+    starts = np.concatenate([starts, np.array([0, C - block], dtype=np.int64)])
+    return np.unique((starts[:, None] + np.arange(block, dtype=np.int64)).reshape(-1))
+
+
+def dump_outputs(work, dirpath: str, steps: int, world: int, rank: int) -> None:
+    """Write what the last of `steps` timed steps left in its parity slot and its decode output (the
+    two arrays a caller of the step receives) as float32 .npy files, at most DUMP_BYTES in all."""
+    slot = (steps - 1) % len(work.parity)
+    par, out = work.parity[slot], work.outs[slot % work.lanes]
+    cols = _dump_columns(work.C, DUMP_BYTES // (4 * (work.k + work.p)))
+    idx = torch.from_numpy(cols).to(par.device)
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, t in (("parity", par), ("decoded", out)):
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), t.index_select(1, idx).cpu().numpy().astype(np.float32))
 
 
 class GpuWorkload:
@@ -984,6 +1042,9 @@ def main(argv=None) -> int:
             stage["at"] = f"weak/{head_mode} headline"
             work, C = weak_work(a, k, n, e_mat, rs.G, pool_t, rank, dev, has_pg)
             head = run_weak_mode(a, work, head_mode, world, dev, has_pg, a.steps, a.warmup, graph=a.graph)
+        if a.dump_outputs:
+            stage["at"] = "writing the outputs"
+            dump_outputs(work, a.dump_outputs, a.steps, world, rank)
         stage["at"] = "headline verification"
         ok = work.verify() and head["ok"]
         okt = torch.tensor([1 if ok else 0], device=dev)
@@ -998,9 +1059,10 @@ def main(argv=None) -> int:
     # issued (the group may be out of step): rank 0 prints and every rank leaves.
     # Order: least collective risk first (e2e: own PCIe link + barriers; none: no traffic; owners:
     # one all_to_all), the point-to-point gathers (strong, root) last.
-    compare = has_pg and not a.no_compare
+    # All of them (and the --configs children) are --full's; a plain run prints the headline record.
+    compare = a.full and has_pg and not a.no_compare
     todo = []
-    if dev.type == "cuda" and not a.no_e2e and not head_strong:
+    if a.full and dev.type == "cuda" and not a.no_e2e and not head_strong:
         todo.append(("e2e", None))
     if compare and not head_strong:
         todo += [("weak", m) for m in ("none", "owners", "bcast") if m != head_mode]
@@ -1058,7 +1120,7 @@ def main(argv=None) -> int:
             done["n"] = len(todo)
     if compare:
         rec["comparisons_complete"] = clean
-    if world == 1 and clean:
+    if a.full and world == 1 and clean:
         run_configs(a, rec)
     emitter.emit(rec)
     if has_pg and clean:

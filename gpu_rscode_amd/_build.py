@@ -44,8 +44,21 @@ def file_lock(shared: bool = False):
     serialise their rebuilds (exclusive) instead of overwriting one module concurrently, and check
     staleness and import under the shared lock, so no rank reads a module while another links it."""
     path = ROOT / "build" / ".lock"
-    path.parent.mkdir(parents=True, exist_ok=True)
-    with open(path, "a") as f:
+    try:
+        path.parent.mkdir(parents=True, exist_ok=True)
+        f = open(path, "a")
+    except OSError:
+        # A tree this user cannot write (built by another account, a read-only mount): flock needs no
+        # write access, so an existing lock file still serialises; with none, nobody here can relink
+        # a module either and there is nothing to wait for.
+        try:
+            f = open(path, "rb")
+        except OSError:
+            f = None
+    if f is None:
+        yield
+        return
+    with f:
         fcntl.flock(f, fcntl.LOCK_SH if shared else fcntl.LOCK_EX)
         try:
             yield

@@ -49,18 +49,18 @@ r_tests() {
   step smoke 300 $PY -c "import __graft_entry__ as g; g.smoke()"
 }
 r_bench() {
-  step bench 300 $PY bench.py --gpus 1 --steps 20 --warmup 5 $BENCH_ARGS &&
+  step bench 300 $PY bench.py --gpus 1 --steps 20 --warmup 5 --full $BENCH_ARGS &&
   step bench_graph 300 $PY bench.py --graph --no-e2e $BENCH_ARGS
 }
 r_presets() {
-  step bench_k128n160 300 $PY bench.py --preset k128n160 --steps 20 &&
-  step bench_k16n20_8g 300 $PY bench.py --preset k16n20_8g --steps 10 &&
-  step bench_k4n6 300 $PY bench.py --preset k4n6 &&
+  step bench_k128n160 300 $PY bench.py --preset k128n160 --steps 20 --full &&
+  step bench_k16n20_8g 300 $PY bench.py --preset k16n20_8g --steps 10 --full &&
+  step bench_k4n6 300 $PY bench.py --preset k4n6 --full &&
   step bench_k16n20_64g 600 $PY bench.py --preset k16n20_64g --steps 5 --warmup 1
 }
 r_rccl() {
   step rccl_probe 180 $PY scripts/rccl_probe.py &&
-  step bench_pg_headline 300 $PY bench.py --force-pg --steps 10 --warmup 2 --no-e2e &&
+  step bench_pg_headline 300 $PY bench.py --force-pg --steps 10 --warmup 2 --no-e2e --full &&
   step bench_pg_strong 300 $PY bench.py --force-pg --scaling strong --steps 10 --warmup 2 --no-e2e
 }
 r_files() {

@@ -28,7 +28,8 @@ def _record(out: str) -> dict:
 
 @pytest.mark.parametrize("gpus", [2, 3])
 def test_launcher_runs_world_ranks_and_reports_every_comm_mode(gpus):
-    r = _run(["--device", "cpu", "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--bytes", str(300_001)])
+    r = _run(["--device", "cpu", "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--bytes", str(300_001),
+              "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["n_gpus"] == gpus and rec["steps"] == 3 and rec["warmup"] == 1
@@ -57,8 +58,8 @@ def test_launcher_runs_world_ranks_and_reports_every_comm_mode(gpus):
 
 def _fault_run(mode, env, gpus=3):
     e = {"GFRS_FAULT_MODE": mode, "GFRS_COMPARE_BUDGET_S": "25", **env}
-    r = _run(["--device", "cpu", "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--bytes", str(200_003)],
-             env=e, timeout=240)
+    r = _run(["--device", "cpu", "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--bytes", str(200_003),
+              "--full"], env=e, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["verified"] is True and rec["value"] > 0 and rec["comparisons_complete"] is False
@@ -106,7 +107,7 @@ def test_strong_scaling_headline(gather):
 
 
 def test_forced_one_rank_group_runs_every_mode():
-    r = _run(["--device", "cpu", "--force-pg", "--steps", "2", "--warmup", "1", "--bytes", str(100_000)])
+    r = _run(["--device", "cpu", "--force-pg", "--steps", "2", "--warmup", "1", "--bytes", str(100_000), "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["n_gpus"] == 1 and rec["config"]["process_group"] is True and rec["verified"] is True
@@ -120,6 +121,63 @@ def test_single_rank_record_and_comm_choice():
     assert rec["n_gpus"] == 1 and rec["config"]["comm"] == "none" and "value_by_comm" not in rec
     for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
         assert key in rec
+
+
+def test_plain_run_times_only_the_headline():
+    """Without --full nothing is timed after the headline: no comparison modes on a process group,
+    no --configs children, and the record still carries the headline's keys."""
+    r = _run(["--device", "cpu", "--force-pg", "--steps", "2", "--warmup", "1", "--bytes", str(100_000),
+              "--configs", "k4n6"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _record(r.stdout)
+    assert rec["verified"] is True and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert set(rec["value_by_comm"]) == {"bcast"} and rec["value"] == rec["value_by_comm"]["bcast"]["GBps"]
+    for key in ("strong", "value_strong", "value_no_comm", "configs", "e2e", "comparisons_complete"):
+        assert key not in rec
+    assert rec["vs_baseline"] is None
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs: parity.npy / decoded.npy hold what the last timed step computed (float32 byte
+    values), the same from run to run, and the parity is the numpy oracle's for the decoded rows."""
+    import numpy as np
+
+    from gpu_rscode_amd import ReedSolomon, gf
+
+    args = ["--device", "cpu", "--steps", "3", "--warmup", "1", "--bytes", str(100_003)]
+    dumps = []
+    for name in ("a", "b"):
+        r = _run([*args, "--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0 and _record(r.stdout)["verified"] is True, r.stderr[-3000:]
+        assert sorted(os.listdir(tmp_path / name)) == ["decoded.npy", "parity.npy"]
+        dumps.append({n: np.load(tmp_path / name / f"{n}.npy") for n in ("parity", "decoded")})
+    a, b = dumps
+    C = (100_003 + 9) // 10
+    assert a["parity"].shape == (4, C) and a["decoded"].shape == (10, C)
+    assert a["parity"].dtype == np.float32 and a["decoded"].dtype == np.float32
+    assert np.array_equal(a["parity"], b["parity"]) and np.array_equal(a["decoded"], b["decoded"])
+    want = gf.GF256.gemm(ReedSolomon(10, 14).E, a["decoded"].astype(np.uint8))
+    assert np.array_equal(a["parity"].astype(np.uint8), want)
+
+
+def test_dump_outputs_samples_long_rows():
+    """Rows longer than the dump's budget: a fixed sample of columns, head and ragged tail included,
+    identical on every call, and within 64 MB as float32 for the widest preset."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for name in ("k10n14", "k128n160", "k16n20_8g"):
+        pr = bench.PRESETS[name]
+        C = (pr["bytes"] + pr["k"] - 1) // pr["k"]
+        cols = bench._dump_columns(C, bench.DUMP_BYTES // (4 * pr["n"]))
+        assert np.array_equal(cols, bench._dump_columns(C, bench.DUMP_BYTES // (4 * pr["n"])))
+        assert cols[0] == 0 and cols[-1] == C - 1 and np.all(np.diff(cols) > 0)
+        assert 4 * pr["n"] * len(cols) <= 64_000_000 and len(cols) > 1000
+    assert np.array_equal(bench._dump_columns(1000, 5000), np.arange(1000))
 
 
 def test_prewarm_runs_local_steps_before_the_warmup():
@@ -162,7 +220,7 @@ def test_gpu_bench_record_with_worst_case_e2e_decode(preset, erased):
     """One rank on the MI355X, 64 MiB: the device step verifies, and the e2e block's decode rebuilds
     the first `erasures` natives (src/unit-test.sh keeps the last k chunks) through the host pipeline,
     and its reference-shaped decode writes all k natives into one pinned file image."""
-    r = _run(["--preset", preset, "--steps", "3", "--warmup", "1", "--bytes", str(64 << 20)], timeout=240)
+    r = _run(["--preset", preset, "--steps", "3", "--warmup", "1", "--bytes", str(64 << 20), "--full"], timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["verified"] is True and rec["n_gpus"] == 1 and rec["config"]["device"] == "cuda"
@@ -173,11 +231,33 @@ def test_gpu_bench_record_with_worst_case_e2e_decode(preset, erased):
 
 
 @pytest.mark.gpu
+def test_gpu_bench_plain_run_dumps_sampled_outputs(tmp_path):
+    """A plain run on the MI355X (no e2e, no configs) with --dump-outputs at 64 MiB: the rows are
+    longer than the dump's budget, so a sample of columns is written; column by column the parity is
+    the numpy oracle's for the decoded natives."""
+    import numpy as np
+
+    from gpu_rscode_amd import ReedSolomon, gf
+
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--bytes", str(64 << 20), "--dump-outputs",
+              str(tmp_path)], timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _record(r.stdout)
+    assert rec["verified"] is True and rec["ms_per_step"] > 0 and "e2e" not in rec and "configs" not in rec
+    par, dec = np.load(tmp_path / "parity.npy"), np.load(tmp_path / "decoded.npy")
+    C = ((64 << 20) + 9) // 10
+    assert par.dtype == np.float32 and par.shape[0] == 4 and dec.shape[0] == 10
+    assert par.shape[1] == dec.shape[1] and 1000 < par.shape[1] < C
+    assert np.array_equal(par.astype(np.uint8), gf.GF256.gemm(ReedSolomon(10, 14).E, dec.astype(np.uint8)))
+
+
+@pytest.mark.gpu
 def test_gpu_bench_forced_rccl_group_every_mode():
     """--force-pg on one MI355X: a one-rank RCCL group runs the per-step pattern broadcast, the owners
     all_to_all (to self), the root grouped send/recv (to self) and the strong-scaling gather — every
     RCCL path of the N > 1 run — and each mode verifies."""
-    r = _run(["--force-pg", "--steps", "4", "--warmup", "1", "--bytes", str(64 << 20), "--no-e2e"], timeout=240)
+    r = _run(["--force-pg", "--steps", "4", "--warmup", "1", "--bytes", str(64 << 20), "--no-e2e", "--full"],
+             timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["verified"] is True and rec["config"]["process_group"] is True
@@ -202,7 +282,7 @@ def test_gpu_bench_three_ranks_rehearsed_on_one_gpu():
     owners all_to_all, root's receive lists and strong scaling's per-row gather into rank 0's full
     rows (point-to-point pieces staged through host memory under gloo)."""
     r = _run(["--gpus", "3", "--pg-backend", "gloo", "--steps", "6", "--warmup", "2", "--bytes", str(32 << 20),
-              "--no-e2e"], timeout=300)
+              "--no-e2e", "--full"], timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     assert rec["verified"] is True and rec["n_gpus"] == 3 and rec["config"]["pg_backend"] == "gloo"
@@ -228,7 +308,7 @@ def test_gpu_bench_three_ranks_strong_headline_rehearsed():
 def test_gpu_bench_fault_in_root_mode_keeps_headline():
     """--force-pg on the MI355X with a fault injected into the root gather: one JSON line, the RCCL
     headline verified, root recorded as an error, the modes before it verified."""
-    r = _run(["--force-pg", "--steps", "4", "--warmup", "1", "--bytes", str(64 << 20), "--no-e2e"],
+    r = _run(["--force-pg", "--steps", "4", "--warmup", "1", "--bytes", str(64 << 20), "--no-e2e", "--full"],
              env={"GFRS_FAULT_MODE": "root"}, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
@@ -252,7 +332,7 @@ def test_configs_children_embed_records_and_survive_a_crash_and_a_hang():
     are embedded under configs. A child that crashes (rc 7) or hangs (killed at its timeout) is
     recorded as an error and the headline record is unchanged and verified."""
     r = _run(["--device", "cpu", "--steps", "2", "--warmup", "1", "--configs", "k4n6,k10n14_w16",
-              "--config-steps", "3", "--config-warmup", "1"])
+              "--config-steps", "3", "--config-warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
     cf = rec["configs"]
@@ -260,7 +340,7 @@ def test_configs_children_embed_records_and_survive_a_crash_and_a_hang():
     assert all(c["verified"] is True and c["steps"] == 3 and c["warmup"] == 1 and c["value"] > 0 for c in cf.values())
     assert "GF(2^16)" in cf["k10n14_w16"]["metric"] and cf["k10n14_w16"]["dtype"].startswith("uint16")
     r = _run(["--device", "cpu", "--steps", "2", "--warmup", "1", "--configs", "k4n6,k10n14_w16",
-              "--config-steps", "2", "--configs-budget", "40"],
+              "--config-steps", "2", "--configs-budget", "40", "--full"],
              env={"GFRS_CONFIG_FAULT": "k4n6:crash"})
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)
@@ -268,7 +348,7 @@ def test_configs_children_embed_records_and_survive_a_crash_and_a_hang():
     assert rec["configs"]["k4n6"]["rc"] == 7 and "error" in rec["configs"]["k4n6"]
     assert rec["configs"]["k10n14_w16"]["verified"] is True
     r = _run(["--device", "cpu", "--steps", "2", "--warmup", "1", "--configs", "k10n14_w16,k4n6",
-              "--config-steps", "2", "--configs-budget", "25"],
+              "--config-steps", "2", "--configs-budget", "25", "--full"],
              env={"GFRS_CONFIG_FAULT": "k10n14_w16:hang"}, timeout=120)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _record(r.stdout)

@@ -54,6 +54,20 @@ def test_file_lock_serialises_processes():
     assert [e[0] for e in ev] == ["in", "out"] * 3  # no two holders at once
 
 
+def test_tree_without_a_writable_lock_file_still_loads(monkeypatch, tmp_path):
+    """A tree whose build/.lock cannot be created (built by another account, a read-only mount; here
+    build is a plain file, which stops root too): the lock is skipped, not an error, and an
+    up-to-date module is imported as it is."""
+    (tmp_path / "build").write_text("")
+    monkeypatch.setattr(_build, "ROOT", tmp_path)
+    with _build.file_lock(shared=True):
+        pass
+    with _build.file_lock():
+        pass
+    calls = _fresh(monkeypatch, stale=False)
+    assert hasattr(_native.cpu(), "encoding_matrix") and calls == []
+
+
 def test_fp4_router_table():
     """The FP4 engine's one routing function (fp4_route, csrc/kernels/gf_mfma_fp4.hip) and its
     override (GFRS_TUNE=fp4=..., parsed among other keys): k = 128 wide-stripe shapes by M-tile count, plain and with fused copies."""
