@@ -46,6 +46,28 @@ hipError_t launch_gf_gemm_variant(const void* desc, int k, int m_pad, int64_t co
 // the < 16-byte tail on the byte kernel.
 hipError_t launch_gf_gemm_lut(const void* desc, int k, int m_pad, int64_t col0, int64_t ncols, hipStream_t stream);
 
+// ---- scrub (csrc/kernels/gf_scrub.hip) ---------------------------------------------------------
+// desc: a desc_layout(n, m_pad) descriptor whose inputs are the n stripe rows (natives first), whose
+// tables are those of the parity-check matrix H = [E | I_p] (p x n, m_pad = pad_m(p)) and whose
+// out_ptr entries are all 0. Computes the syndrome H . stripe over byte columns [0, ncols) without
+// storing it and sets bit i % 32 of mask[b] when syndrome row i is nonzero anywhere in columns
+// [b * block_bytes, (b + 1) * block_bytes); block_bytes is a power of two >= 4096 and mask holds
+// ceil(ncols / block_bytes) words, zeroed here first. A consistent stripe stores nothing else.
+// force_bytewise: rows that are not 16-byte aligned. Any n <= 256, any p. ident: H's last `ident`
+// columns are promised to be the identity (p for H = [E | I_p], 0 for an arbitrary H): the
+// rows-in-flight kernel of the narrow codes then XORs those rows in without a multiply.
+hipError_t launch_gf_syndrome(const void* desc, int n, int m_pad, int ident, int64_t ncols, bool force_bytewise,
+                              int64_t block_bytes, int32_t* mask, hipStream_t stream);
+// Classifies every byte column of the column blocks whose mask word is nonzero (p <= 16; same desc).
+// loc (device): H row-major (p x n bytes), then per column j its pivot row (first nonzero row, n
+// bytes) and the inverse of that pivot (n bytes). counts (device, zeroed here first): votes[n],
+// then the unlocated columns, then the inconsistent columns. A column with one nonzero syndrome
+// byte s_i votes for parity chunk n - p + i; with several, for the native j with s == e . H[:, j],
+// e = s_r / H[r][j], r = j's pivot row; otherwise (or when !locatable) it is unlocated.
+hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
+                            const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
+                            hipStream_t stream);
+
 // ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip) ---------------------------------------
 // Inverts `batch` n x n matrices (row-major, contiguous) with row pivoting, one workgroup each,
 // [A|I] resident in LDS. status[b] = 0 ok, 1 singular. n <= 256.

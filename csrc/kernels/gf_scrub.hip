@@ -1,0 +1,482 @@
+// Scrub on gfx950: is an n-row stripe consistent, and if not, which chunk is wrong?
+//
+// With the parity-check matrix H = [E | I_p] (p x n) the syndrome of byte column c is
+// s = H . stripe[:, c]: zero exactly when the column is consistent, and a multiple of column j of H
+// when only chunk j is wrong there. Two kernels:
+//   * gf_syndrome_*: the hot path. The same GF-GEMM as gf_gemm.hip (perm_device.h helpers,
+//     non-temporal 16-byte loads, output tiles of up to 16 rows, the XCD tile map) over a descriptor
+//     whose inputs are the n stripe rows and whose tables are H's, but no row is ever stored: every
+//     lane folds its accumulators to one bit per syndrome row, a wave ORs them with ballots, and lane
+//     0 issues one atomicOr into the int32 mask word of its column block, only when a bit is set.
+//     A clean stripe reads its n rows and stores nothing (ReedSolomon.verify: k rows read, p
+//     written, 2 p read back).
+//   * gf_locate_kernel: the cold path. Workgroups whose mask word is zero exit at once; the others
+//     recompute the syndrome of each byte column and classify it: one nonzero s_i blames parity
+//     chunk k + i; several blame the native j with s == e . H[:, j], e = s_r / H[r][j], r = column
+//     j's pivot row; anything else is unlocated. Counts go through an LDS histogram per workgroup
+//     and one 64-bit atomic add per nonzero bin.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <type_traits>
+
+#include "gfrs/desc.h"
+#include "gfrs/kernels.h"
+#include "gfrs/perm_device.h"
+#include "gfrs/tune.h"
+
+namespace gfrs {
+namespace {
+
+using namespace permdev;
+
+__constant__ Tables d_tab = make_tables();
+
+// Syndrome accumulators of one lane's column unit: T = uint8_t (one byte column, any alignment;
+// only the low byte of each accumulator is meaningful) or uint32_t (four columns, 4-byte aligned).
+// The row loads are issued 8 at a time before any is used, as gf_gemm.hip's tail_byte does.
+template <int MT, typename T>
+__device__ __forceinline__ void syn_cols(const DescView& d, int n, int m_pad, int i0, int64_t off,
+                                         uint32_t (&acc)[MT]) {
+  constexpr int kB = 8;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) acc[i] = 0;
+  for (int j0 = 0; j0 < n; j0 += kB) {
+    T x[kB];
+#pragma unroll
+    for (int u = 0; u < kB; ++u) x[u] = j0 + u < n ? *(gptr<const T>)(d.in[j0 + u] + uint64_t(off)) : T(0);
+#pragma unroll
+    for (int u = 0; u < kB; ++u) {
+      const int j = j0 + u;
+      if (j < n) {
+        const Sel s = make_sel(x[u]);
+        const auto t = d.tab + (size_t(j) * m_pad + i0) * kPermStride;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = mac_map(acc[i], t + i * kPermStride, s);
+      }
+    }
+  }
+}
+
+// bit i: syndrome row i0 + i is nonzero in this byte column
+template <int MT>
+__device__ __forceinline__ uint32_t syn_byte_bits(const DescView& d, int n, int m_pad, int i0, int64_t off) {
+  uint32_t acc[MT];
+  syn_cols<MT, uint8_t>(d, n, m_pad, i0, off, acc);
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) bits |= uint32_t((acc[i] & 0xFFu) != 0) << i;
+  return bits;
+}
+
+template <int MT>
+__device__ __forceinline__ uint32_t group_bits(const uint32_t (&acc)[MT][4]) {
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) bits |= uint32_t((acc[i][0] | acc[i][1] | acc[i][2] | acc[i][3]) != 0) << i;
+  return bits;
+}
+
+// OR of the wave's row bits into mask word `blk` (wave-uniform): one ballot when the wave is clean,
+// else one per row and a single atomicOr from lane 0. Called with the whole wave converged.
+template <int MT>
+__device__ __forceinline__ void wave_or(uint32_t rowbits, int shift, int* mask, int64_t blk) {
+  if (__builtin_amdgcn_ballot_w64(rowbits != 0) == 0) return;
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+    if (__builtin_amdgcn_ballot_w64(((rowbits >> i) & 1u) != 0) != 0) bits |= 1u << i;
+  if ((threadIdx.x & 63u) == 0) atomicOr(mask + blk, int(bits << shift));
+}
+
+// The mask word of a wave of 16-byte-group lanes whose first lane owns group g0: every group of the
+// wave lies in one 4096-byte span (a workgroup's 256 groups), which block_bytes >= 4096 never
+// splits, and the ragged tail bytes (lanes ngroups .. ngroups + tail - 1) sit right after group
+// ngroups - 1, in the span of group `ngroups`.
+__device__ __forceinline__ int64_t wave_block(int64_t g0, int64_t ngroups, int bshift) {
+  return ((g0 < ngroups ? g0 : ngroups) * 16) >> bshift;
+}
+
+// General form: any n, two rows in flight, grid-stride over column blocks (gf_gemm_vec_kernel with
+// V = 1, PF = 2, non-temporal loads, no copies and no stores).
+template <int MT>
+__global__ __launch_bounds__(kBlock) void gf_syndrome_vec_kernel(DescView d, int n, int m_pad, int ntiles,
+                                                                 int64_t ngroups, int64_t nblk, int64_t ncb, int tail,
+                                                                 int* mask, int bshift) {
+  const TileMap tm = map_block(ntiles);
+  if (tm.cb0 >= ncb) return;
+  const int i0 = tm.tile * MT;
+  constexpr bool kPairs = MT <= 8;  // as gf_gemm_vec_kernel: the 16-row tile has no registers for pairs
+  for (int64_t cb = tm.cb0; cb < nblk; cb += ncb) {
+    const int64_t g = cb * kBlock + threadIdx.x;
+    uint32_t rowbits = 0;
+    if (g < ngroups) {
+      const int64_t off = g * 16;
+      uint32_t acc[MT][4];
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) acc[i][w] = 0;
+      u32x4 r0 = ld16<true>(row_vec(d.in[0], off));
+      u32x4 r1 = n > 1 ? ld16<true>(row_vec(d.in[1], off)) : u32x4{0u, 0u, 0u, 0u};
+      for (int j = 0; j < n; j += 2) {
+        const u32x4 x0 = r0, x1 = r1;
+        if (j + 2 < n) r0 = ld16<true>(row_vec(d.in[j + 2], off));
+        if (j + 3 < n) r1 = ld16<true>(row_vec(d.in[j + 3], off));
+        const auto t0 = d.tab + (size_t(j) * m_pad + i0) * kPermStride;
+        const auto t1 = t0 + size_t(m_pad) * kPermStride;
+        if (kPairs && j + 1 < n) {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            const Sel s0 = make_sel(x0[w]);
+            const Sel s1 = make_sel(x1[w]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+              acc[i][w] = mac_pair(acc[i][w], t0 + i * kPermStride, s0, t1 + i * kPermStride, s1);
+          }
+        } else {
+#pragma unroll
+          for (int w = 0; w < 4; ++w) {
+            const Sel s0 = make_sel(x0[w]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][w] = mac_map(acc[i][w], t0 + i * kPermStride, s0);
+          }
+          if (j + 1 < n) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+              const Sel s1 = make_sel(x1[w]);
+#pragma unroll
+              for (int i = 0; i < MT; ++i) acc[i][w] = mac_map(acc[i][w], t1 + i * kPermStride, s1);
+            }
+          }
+        }
+      }
+      rowbits = group_bits<MT>(acc);
+    } else if (g - ngroups < tail) {
+      rowbits = syn_byte_bits<MT>(d, n, m_pad, i0, ngroups * 16 + (g - ngroups));
+    }
+    wave_or<MT>(rowbits, i0 & 16, mask, wave_block(cb * kBlock + (threadIdx.x & ~63u), ngroups, bshift));
+  }
+}
+
+// Rows-in-flight form (narrow codes, compile-time N, one tile): every lane issues the loads of all N
+// rows of its group before the first multiply. It is gf_gemm_rows_lat_kernel without copies and
+// stores: the table pointer is re-issued by an empty asm after each row pair's math, so each pair's
+// scalar table loads wait only for the previous pair and nothing spills; one group per lane, no
+// grid-stride loop (around a loop the loop-invariant table words would be hoisted and spilled).
+// IDENT: the last MT columns of H are the identity (H = [E | I_p], p = MT), so parity row i is
+// XORed into syndrome row i as it is instead of going through the tables of 0 and 1: the multiplies
+// of an encode (k x p) are left, not n x p.
+template <int MT, int N, bool IDENT>
+__global__ __launch_bounds__(kBlock) void gf_syndrome_rows_kernel(DescView d, int n_tail, int m_pad, int ntiles,
+                                                                  int64_t ngroups, int tail, int* mask, int bshift) {
+  constexpr int K = IDENT ? N - MT : N;  // rows that are multiplied
+  const TileMap tm = map_block(ntiles);
+  const int i0 = sgpr_int(tm.tile * MT);
+  const int64_t g = tm.cb0 * kBlock + threadIdx.x;
+  uint32_t rowbits = 0;
+  if (g < ngroups) {
+    const int64_t off = g * 16;
+    u32x4 x[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = ld16<true>(row_vec(d.in[j], off));
+    uint32_t acc[MT][4];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) acc[i][w] = 0;
+    uint64_t tb = (uint64_t)d.tab;
+#pragma unroll
+    for (int j = 0; j < K; j += 2) {
+      if (j > 0) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int w = 0; w < 4; ++w) asm volatile("" ::"v"(acc[i][w]));
+      }
+      asm volatile("" : "+s"(tb));
+      asm volatile("" : "+v"(x[j]));
+      if (j + 1 < K) asm volatile("" : "+v"(x[j + 1]));
+      const auto t0 = (cptr<uint32_t>)tb + (size_t(j) * m_pad + i0) * kPermStride;
+      if (j + 1 < K) {
+        const auto t1 = t0 + size_t(m_pad) * kPermStride;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const Sel s0 = make_sel(x[j][w]);
+          const Sel s1 = make_sel(x[j + 1][w]);
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+            acc[i][w] = mac_pair(acc[i][w], t0 + i * kPermStride, s0, t1 + i * kPermStride, s1);
+        }
+      } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const Sel s = make_sel(x[j][w]);
+#pragma unroll
+          for (int i = 0; i < MT; ++i) acc[i][w] = mac_map(acc[i][w], t0 + i * kPermStride, s);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (IDENT) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) acc[i][w] ^= x[K + i][w];
+    }
+    rowbits = group_bits<MT>(acc);
+  } else if (g - ngroups < tail) {
+    // (n_tail == N, passed at run time: a compile-time N would unroll the tail's row loop too)
+    rowbits = syn_byte_bits<MT>(d, n_tail, m_pad, i0, ngroups * 16 + (g - ngroups));
+  }
+  wave_or<MT>(rowbits, i0 & 16, mask, wave_block(tm.cb0 * kBlock + (threadIdx.x & ~63u), ngroups, bshift));
+}
+
+// Byte form: one lane per byte column, rows of any alignment. A wave's 64 columns share a mask word
+// (block_bytes is a multiple of 64).
+template <int MT>
+__global__ __launch_bounds__(kBlock) void gf_syndrome_byte_kernel(DescView d, int n, int m_pad, int ntiles,
+                                                                  int64_t ncols, int64_t nblk, int64_t ncb, int* mask,
+                                                                  int bshift) {
+  const TileMap tm = map_block(ntiles);
+  if (tm.cb0 >= ncb) return;
+  const int i0 = tm.tile * MT;
+  for (int64_t cb = tm.cb0; cb < nblk; cb += ncb) {
+    const int64_t c = cb * kBlock + threadIdx.x;
+    const uint32_t rowbits = c < ncols ? syn_byte_bits<MT>(d, n, m_pad, i0, c) : 0u;
+    const int64_t c0 = cb * kBlock + (threadIdx.x & ~63u);
+    wave_or<MT>(rowbits, i0 & 16, mask, (c0 < ncols ? c0 : 0) >> bshift);
+  }
+}
+
+// ---- locate -----------------------------------------------------------------------------------
+constexpr int kLocSpanShift = 14;  // a workgroup covers min(block_bytes, 16 KiB) columns
+
+struct LocLds {
+  uint8_t exp[1024];         // gf256.h layout: exp[510..1020] = 0
+  uint16_t log[256];         // log[0] = 510
+  uint16_t hlog[16 * 256];   // log H[i][j] at [i * n + j]
+  uint16_t pinvlog[256];     // log of 1 / H[piv[j]][j]
+  uint8_t piv[256];          // pivot (first nonzero) row of column j
+  uint32_t hist[256 + 2];    // votes[n], unlocated, bad columns
+};
+
+// One byte column: s_i = byte q of acc[i]. Votes go to the LDS histogram, the two totals to the
+// lane's own counters.
+template <int MT>
+__device__ __forceinline__ void classify(const LocLds& l, uint32_t* hist, const uint32_t (&acc)[MT], int q, int n,
+                                         int p, bool locatable, uint32_t& bad, uint32_t& unl) {
+  uint32_t sp[4] = {0u, 0u, 0u, 0u};  // the syndrome bytes, four rows per word
+  uint32_t nz = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const uint32_t s = (acc[i] >> (8 * q)) & 0xFFu;
+    sp[i >> 2] |= s << (8 * (i & 3));
+    nz |= uint32_t(s != 0) << i;
+  }
+  if (nz == 0) return;
+  ++bad;
+  if (!locatable) {
+    ++unl;
+    return;
+  }
+  const int k = n - p;
+  if ((nz & (nz - 1)) == 0) {
+    atomicAdd(&hist[k + (__ffs(int(nz)) - 1)], 1u);
+    return;
+  }
+  for (int j = 0; j < k; ++j) {
+    const int r = l.piv[j];
+    const uint32_t w = r < 8 ? (r < 4 ? sp[0] : sp[1]) : (r < 12 ? sp[2] : sp[3]);
+    const uint32_t sr = (w >> (8 * (r & 3))) & 0xFFu;
+    if (sr == 0) continue;  // e would be 0
+    int le = int(l.log[sr]) + int(l.pinvlog[j]);  // log e, e = s_r / H[r][j]
+    if (le >= 255) le -= 255;
+    bool match = true;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      if (i < p) {
+        const uint32_t s = (sp[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+        match = match && uint32_t(l.exp[le + int(l.hlog[i * n + j])]) == s;
+      }
+    }
+    if (match) {
+      atomicAdd(&hist[j], 1u);
+      return;
+    }
+  }
+  ++unl;
+}
+
+template <int MT>
+__global__ __launch_bounds__(kBlock) void gf_locate_kernel(DescView d, int n, int p, int64_t ncols, int bshift,
+                                                           int span_shift, const int* mask, const uint8_t* loc,
+                                                           int locatable, int bytewise, unsigned long long* counts) {
+  const int64_t base = int64_t(blockIdx.x) << span_shift;
+  if (mask[base >> bshift] == 0) return;  // (uniform: the whole workgroup leaves before any barrier)
+  __shared__ LocLds l;
+  for (int t = threadIdx.x; t < 1024; t += kBlock) l.exp[t] = t < kExpLen ? d_tab.exp[t] : uint8_t(0);
+  for (int t = threadIdx.x; t < 256; t += kBlock) l.log[t] = d_tab.log[t];
+  for (int t = threadIdx.x; t < p * n; t += kBlock) l.hlog[t] = d_tab.log[loc[t]];
+  for (int t = threadIdx.x; t < n; t += kBlock) {
+    l.piv[t] = loc[p * n + t];
+    l.pinvlog[t] = d_tab.log[loc[p * n + n + t]];
+  }
+  for (int t = threadIdx.x; t < n + 2; t += kBlock) l.hist[t] = 0;
+  __syncthreads();
+
+  const int64_t end = std::min(base + (int64_t(1) << span_shift), ncols);
+  uint32_t bad = 0, unl = 0;
+  uint32_t acc[MT];
+  if (!bytewise) {
+    for (int64_t c = base + int64_t(threadIdx.x) * 4; c < end; c += kBlock * 4) {
+      if (c + 4 <= end) {
+        syn_cols<MT, uint32_t>(d, n, MT, 0, c, acc);
+        for (int q = 0; q < 4; ++q) classify<MT>(l, l.hist, acc, q, n, p, locatable != 0, bad, unl);
+      } else {
+        for (int64_t cc = c; cc < end; ++cc) {
+          syn_cols<MT, uint8_t>(d, n, MT, 0, cc, acc);
+          classify<MT>(l, l.hist, acc, 0, n, p, locatable != 0, bad, unl);
+        }
+      }
+    }
+  } else {
+    for (int64_t c = base + threadIdx.x; c < end; c += kBlock) {
+      syn_cols<MT, uint8_t>(d, n, MT, 0, c, acc);
+      classify<MT>(l, l.hist, acc, 0, n, p, locatable != 0, bad, unl);
+    }
+  }
+  if (unl) atomicAdd(&l.hist[n], unl);
+  if (bad) atomicAdd(&l.hist[n + 1], bad);
+  __syncthreads();
+  for (int t = threadIdx.x; t < n + 2; t += kBlock) {
+    const uint32_t v = l.hist[t];
+    if (v) atomicAdd(counts + t, (unsigned long long)v);
+  }
+}
+
+// ---- launch -----------------------------------------------------------------------------------
+struct Grid {
+  int64_t nblk, ncb;
+  unsigned blocks;
+};
+
+// as gf_gemm.hip's make_grid: at most 2^32 - 1 work-items along x, column blocks padded to a multiple
+// of 8 for the XCD map (short grids unpadded)
+constexpr int64_t kMaxGridBlocks = int64_t(UINT32_MAX) / kBlock;
+inline Grid make_grid(int64_t items, int ntiles) {
+  Grid g{};
+  g.nblk = (items + kBlock - 1) / kBlock;
+  g.ncb = std::min(g.nblk, kMaxGridBlocks / ntiles / 8 * 8);
+  const int64_t ncb8 = g.ncb < 8 ? g.ncb : (g.ncb + 7) / 8 * 8;
+  g.blocks = static_cast<unsigned>(ncb8 * ntiles);
+  return g;
+}
+
+template <typename F>
+hipError_t dispatch_tile(int t, F&& f) {
+  switch (t) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+
+inline int log2_exact(int64_t v) {
+  int s = 0;
+  while ((int64_t(1) << s) < v) ++s;
+  return (int64_t(1) << s) == v ? s : -1;
+}
+
+// The rows-in-flight form is built for the (4, 6) and (10, 14) codes, one tile each; `ident` = the
+// trailing identity columns of H, and with ident == MT the parity rows skip the multiplies.
+// GFRS_TUNE=scrub_rows=0 keeps every launch on the general form, scrub_ident=0 multiplies the
+// identity columns too (A/B measurements, profiles/scrub).
+template <int MT, int N>
+void launch_rows_n(const DescView& d, int m_pad, int ident, const Grid& g, int64_t ngroups, int tail, int* mask,
+                   int bshift, hipStream_t stream) {
+  if (ident == MT && tune_int("scrub_ident", 1) != 0)
+    gf_syndrome_rows_kernel<MT, N, true><<<g.blocks, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
+  else
+    gf_syndrome_rows_kernel<MT, N, false><<<g.blocks, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
+}
+
+template <int MT>
+bool launch_rows(const DescView& d, int n, int m_pad, int ident, const Grid& g, int64_t ngroups, int tail, int* mask,
+                 int bshift, hipStream_t stream) {
+  if (m_pad != MT || g.ncb < g.nblk || tune_int("scrub_rows", 1) == 0) return false;
+  if constexpr (MT == 2) {
+    if (n == 6) {
+      launch_rows_n<2, 6>(d, m_pad, ident, g, ngroups, tail, mask, bshift, stream);
+      return true;
+    }
+  }
+  if constexpr (MT == 4) {
+    if (n == 14) {
+      launch_rows_n<4, 14>(d, m_pad, ident, g, ngroups, tail, mask, bshift, stream);
+      return true;
+    }
+  }
+  return false;
+}
+
+bool scrub_args_ok(int n, int m_pad, int64_t ncols, int64_t block_bytes) {
+  return n >= 1 && n <= 256 && m_pad >= 1 && m_pad % tile_for(m_pad) == 0 && ncols >= 0 && block_bytes >= 4096 &&
+         log2_exact(block_bytes) > 0;
+}
+
+}  // namespace
+
+hipError_t launch_gf_syndrome(const void* desc, int n, int m_pad, int ident, int64_t ncols, bool force_bytewise,
+                              int64_t block_bytes, int32_t* mask, hipStream_t stream) {
+  if (!scrub_args_ok(n, m_pad, ncols, block_bytes) || !mask || ident < 0 || ident > m_pad || ident >= n)
+    return hipErrorInvalidValue;
+  if (ncols == 0) return hipSuccess;
+  const int bshift = log2_exact(block_bytes);
+  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
+  hipError_t e = hipMemsetAsync(mask, 0, size_t(nmask) * sizeof(int32_t), stream);
+  if (e != hipSuccess) return e;
+  const DescView d = view(desc, n, m_pad);
+  return dispatch_tile(tile_for(m_pad), [&](auto mt) -> hipError_t {
+    constexpr int MT = decltype(mt)::value;
+    const int ntiles = m_pad / MT;
+    if (force_bytewise) {
+      const Grid g = make_grid(ncols, ntiles);
+      gf_syndrome_byte_kernel<MT><<<g.blocks, kBlock, 0, stream>>>(d, n, m_pad, ntiles, ncols, g.nblk, g.ncb, mask, bshift);
+      return hipGetLastError();
+    }
+    const int64_t ngroups = ncols / 16;
+    const int tail = int(ncols % 16);
+    const Grid g = make_grid(ngroups + tail, ntiles);  // one extra lane per ragged tail byte
+    if (!launch_rows<MT>(d, n, m_pad, ident, g, ngroups, tail, mask, bshift, stream))
+      gf_syndrome_vec_kernel<MT>
+          <<<g.blocks, kBlock, 0, stream>>>(d, n, m_pad, ntiles, ngroups, g.nblk, g.ncb, tail, mask, bshift);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
+                            const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
+                            hipStream_t stream) {
+  if (p < 1 || p > 16 || p >= n || !scrub_args_ok(n, pad_m(p), ncols, block_bytes) || !mask || !loc || !counts)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counts, 0, size_t(n + 2) * sizeof(uint64_t), stream);
+  if (e != hipSuccess || ncols == 0) return e;
+  const int bshift = log2_exact(block_bytes);
+  const int span_shift = std::min(bshift, kLocSpanShift);
+  const int64_t nwg = (ncols + (int64_t(1) << span_shift) - 1) >> span_shift;
+  if (nwg > int64_t(INT32_MAX)) return hipErrorInvalidValue;
+  const DescView d = view(desc, n, pad_m(p));
+  return dispatch_tile(pad_m(p), [&](auto mt) -> hipError_t {
+    constexpr int MT = decltype(mt)::value;
+    gf_locate_kernel<MT><<<unsigned(nwg), kBlock, 0, stream>>>(d, n, p, ncols, bshift, span_shift, mask, loc,
+                                                               locatable ? 1 : 0, force_bytewise ? 1 : 0,
+                                                               reinterpret_cast<unsigned long long*>(counts));
+    return hipGetLastError();
+  });
+}
+
+}  // namespace gfrs

@@ -107,6 +107,27 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("col0"), py::arg("ncols"), py::arg("vec"),
       py::arg("pf") = 2, py::arg("nt") = false, py::arg("max_blocks") = 0, py::arg("stream") = 0);
   m.def(
+      "syndrome",
+      [](uint64_t desc, int n, int m_pad, int ident, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask,
+         uint64_t stream) {
+        check(launch_gf_syndrome(reinterpret_cast<const void*>(desc), n, m_pad, ident, ncols, bytewise, block_bytes,
+                                 reinterpret_cast<int32_t*>(mask), as_stream(stream)),
+              "gf_syndrome");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("m_pad"), py::arg("ident"), py::arg("ncols"), py::arg("bytewise"),
+      py::arg("block_bytes"), py::arg("mask"), py::arg("stream") = 0);
+  m.def(
+      "locate",
+      [](uint64_t desc, int n, int p, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask, uint64_t loc,
+         bool locatable, uint64_t counts, uint64_t stream) {
+        check(launch_gf_locate(reinterpret_cast<const void*>(desc), n, p, ncols, bytewise, block_bytes,
+                               reinterpret_cast<const int32_t*>(mask), reinterpret_cast<const uint8_t*>(loc), locatable,
+                               reinterpret_cast<uint64_t*>(counts), as_stream(stream)),
+              "gf_locate");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("p"), py::arg("ncols"), py::arg("bytewise"), py::arg("block_bytes"),
+      py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("counts"), py::arg("stream") = 0);
+  m.def(
       "invert",
       [](uint64_t a, uint64_t a_inv, int n, int batch, uint64_t status, uint64_t desc, uint64_t sel_rows, int mm,
          int m_pad, uint64_t stream) {

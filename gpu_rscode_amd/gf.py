@@ -271,3 +271,70 @@ def quad_apply16(quad: np.ndarray, x: np.ndarray) -> np.ndarray:
     ol = perm_apply(quad[0], lo) ^ perm_apply(quad[2], hi)
     oh = perm_apply(quad[1], lo) ^ perm_apply(quad[3], hi)
     return (ol.astype(np.uint16) | (oh.astype(np.uint16) << 8)).astype(np.uint16)
+
+
+# ---- scrub: syndrome check and corrupt-chunk location ----------------------------------------------
+def check_matrix(e: np.ndarray) -> np.ndarray:
+    """The p x n parity-check matrix H = [E | I_p] of the systematic code with encoding block E:
+    H . [data; parity] = 0 exactly for a consistent stripe (characteristic 2: E.data ^ parity)."""
+    e = np.asarray(e, dtype=np.uint8)
+    return np.hstack([e, np.eye(e.shape[0], dtype=np.uint8)])
+
+
+def columns_independent(h: np.ndarray) -> bool:
+    """True when no column of H is zero and no two are multiples of each other: a one-chunk error
+    then has a syndrome that names its chunk."""
+    h = np.asarray(h, dtype=np.int64)
+    seen = set()
+    for j in range(h.shape[1]):
+        col = h[:, j]
+        nz = np.nonzero(col)[0]
+        if nz.size == 0:
+            return False
+        key = tuple(int(v) for v in GF256.mul(col, int(GF256.inv(int(col[nz[0]])))))  # first nonzero scaled to 1
+        if key in seen:
+            return False
+        seen.add(key)
+    return True
+
+
+def scrub_oracle(h: np.ndarray, rows, block_bytes: int = 65536):
+    """Plain numpy scrub of an n-row stripe against the check matrix ``h`` (p x n): returns
+    ``(mask, votes, unlocated, bad_columns)``.
+
+    ``mask[b]`` has bit ``i % 32`` set when syndrome row i is nonzero anywhere in columns
+    ``[b * block_bytes, (b + 1) * block_bytes)``. Every column with a nonzero syndrome s is counted
+    in ``bad_columns`` and classified: one nonzero ``s_i`` votes for parity chunk ``k + i``; several
+    vote for the native chunk j whose column of ``h`` s is a multiple of; anything else, and every
+    bad column when p < 2 or the columns of ``h`` are not pairwise independent, is ``unlocated``."""
+    h = np.asarray(h, dtype=np.uint8)
+    p, n = h.shape
+    k = n - p
+    data = np.stack([np.asarray(r, dtype=np.uint8) for r in rows]) if not isinstance(rows, np.ndarray) else rows
+    c = data.shape[1]
+    s = GF256.gemm(h, data)
+    nblk = -(-c // block_bytes)
+    bits = np.zeros(nblk, dtype=np.uint32)
+    for i in range(p):
+        bits[np.unique(np.nonzero(s[i])[0] // block_bytes)] |= np.uint32(1 << (i % 32))
+    mask = bits.view(np.int32)
+    votes = np.zeros(n, dtype=np.int64)
+    nzc = (s != 0).sum(axis=0)
+    bad = nzc > 0
+    bad_columns = int(bad.sum())
+    if p < 2 or not columns_independent(h):
+        return mask, votes, bad_columns, bad_columns
+    single = nzc == 1
+    for i in range(p):
+        votes[k + i] = int((single & (s[i] != 0)).sum())
+    pending = nzc > 1
+    for j in range(k):
+        col = h[:, j]
+        r = int(np.nonzero(col)[0][0])
+        e = GF256.mul(s[r], int(GF256.inv(int(col[r]))))
+        match = pending & (e != 0)
+        for i in range(p):
+            match &= GF256.mul(e, int(col[i])) == s[i]
+        votes[j] = int(match.sum())
+        pending &= ~match
+    return mask, votes, int(pending.sum()), bad_columns

@@ -23,6 +23,8 @@ from .._native import cpu, hip
 from ..ops.gemm import Gemm16Plan, GemmPlan, _rows
 from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, decode_system_into_plan
 from ..ops.matrix import decode_matrix, encoding_matrix
+from ..ops.scrub import (MAX_LOCATE_P, ScrubPlan, ScrubReport, check_block_bytes, cpu_scrub, make_report,
+                         stripe_rows)
 
 PITCH = 256
 
@@ -545,6 +547,85 @@ class ReedSolomon:
         else:
             self._cpu_gemm(coeff, ins, outs)
         return stripe
+
+    # ---- scrub -------------------------------------------------------------------------------
+    @property
+    def H(self) -> np.ndarray:
+        """The p x n parity-check matrix [E | I_p]: H . [data; parity] = 0 for a consistent stripe."""
+        return gf.check_matrix(self.E)
+
+    def _scrub_setup(self, stripe, block_bytes: int, what: str):
+        if self.field != "gf256":
+            raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
+        rows, ncols, dev = stripe_rows(stripe, self.n)
+        block_bytes = check_block_bytes(block_bytes)
+        plan = None
+        if dev.type == "cuda" and self.p > 0:
+            key = self._key(("scrub", block_bytes), rows)
+            plan = self._plans.get(key)
+            if plan is None:
+                plan = self._plans[key] = ScrubPlan(rows, self.H, block_bytes)
+        return rows, ncols, dev, block_bytes, plan
+
+    def syndrome_mask(self, stripe, block_bytes: int = 65536, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """Which column blocks of an n-row stripe (natives first, as for :meth:`reconstruct`) are
+        inconsistent: an int32 tensor ``[ceil(C / block_bytes)]`` on the stripe's device, bit
+        ``i % 32`` set where row i of the syndrome ``H . stripe`` is nonzero in that block; all zero
+        for a consistent stripe. One fused pass that reads the n rows once and stores nothing but
+        the mask; no host sync. Only columns ``[0, C)`` count (pitch padding is never read).
+        ``block_bytes`` is a power of two >= 4096."""
+        rows, ncols, dev, block_bytes, plan = self._scrub_setup(stripe, block_bytes, "syndrome_mask")
+        if plan is not None:
+            return plan.syndrome_mask(stream)
+        if dev.type == "cuda":  # p = 0: nothing to check
+            return torch.zeros(-(-ncols // block_bytes), dtype=torch.int32, device=dev)
+        return cpu_scrub(self.H, rows, ncols, block_bytes, self._cpu_gemm, locate=False)[0]
+
+    def scrub(self, stripe, block_bytes: int = 65536, stream: torch.cuda.Stream | None = None) -> ScrubReport:
+        """Check a stripe and name the chunks that are wrong: :meth:`syndrome_mask`, then every byte
+        column of the dirty blocks is classified. A column whose syndrome has one nonzero byte
+        ``s_i`` votes for parity chunk ``k + i``; one whose syndrome is a multiple of column j of
+        ``H`` votes for native chunk j; any other is counted as unlocated (more than one chunk
+        wrong in that column). Returns a :class:`~gpu_rscode_amd.ops.scrub.ScrubReport`; on the GPU
+        both kernels run back to back with one sync at the end.
+
+        Location needs the columns of ``H`` to be pairwise independent and p >= 2 (checked when the
+        plan is built); otherwise every bad column is unlocated and ``suspects`` is empty. Codes
+        with p > 16 raise ``NotImplementedError`` (``syndrome_mask`` still works)."""
+        rows, ncols, dev, block_bytes, plan = self._scrub_setup(stripe, block_bytes, "scrub")
+        if self.p > MAX_LOCATE_P:
+            raise NotImplementedError(f"scrub locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
+                                      "syndrome_mask works for any p")
+        if plan is not None:
+            return plan.scrub(stream)
+        if dev.type == "cuda":
+            return make_report(np.zeros(self.n, dtype=np.int64), 0, 0,
+                               torch.zeros(-(-ncols // block_bytes), dtype=torch.int32, device=dev))
+        mask, votes, unlocated, bad = cpu_scrub(self.H, rows, ncols, block_bytes, self._cpu_gemm)
+        return make_report(votes, unlocated, bad, mask)
+
+    def heal(self, stripe, report: ScrubReport | None = None) -> ScrubReport:
+        """Repair a stripe in place from its own redundancy. Scrubs if no ``report`` is given; a
+        clean stripe returns the report. If any column is unlocated, or there are no suspects or
+        more than p of them, raises :class:`UnrecoverableError` with the stripe byte-for-byte
+        unchanged. Otherwise rewrites the suspects with ``reconstruct(stripe, erased=suspects)``,
+        scrubs again and returns that second report: read ``.clean`` from it.
+
+        A column with two wrong chunks is told from one with a single wrong chunk only while no three
+        columns of ``H`` are dependent. With p = 2 every three are, so a double error can imitate a
+        single one: the stripe is then "healed" into a consistent but wrong one."""
+        if self.field != "gf256":
+            raise NotImplementedError(f"heal is implemented for field='gf256', not {self.field!r}")
+        if report is None:
+            report = self.scrub(stripe)
+        if report.clean:
+            return report
+        if report.unlocated > 0 or not report.suspects or len(report.suspects) > self.p:
+            raise UnrecoverableError(
+                f"{report.bad_columns} inconsistent columns, {report.unlocated} of them unlocated, "
+                f"suspects {report.suspects}: not repairable from p={self.p} parity chunks")
+        self.reconstruct(stripe, erased=report.suspects)
+        return self.scrub(stripe)
 
     def verify(self, data, parity) -> bool:
         """True when ``parity`` is the encoding of ``data`` (recomputes and compares)."""

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Time the fused syndrome check against the checks the codec had before it.
+
+One process, one device-resident stripe in ``alloc_rows`` buffers (default: the headline shape,
+k=10, n=14, C = 107,374,183). After a warm-up of every call it alternates, round by round,
+
+  * ``syndrome_mask``                  (n rows read, nothing stored on a clean stripe),
+  * ``syndrome_mask`` with the parity rows multiplied by H's identity block (GFRS_TUNE=scrub_ident=0)
+    and on the general kernel (GFRS_TUNE=scrub_rows=0): the A/B of the two kernel choices,
+  * ``verify(data, parity)``           (k rows read and p written by the encode, 2 p read back),
+  * ``encode``                         (k rows read, p written),
+
+each timed with device events over ``--reps`` calls, and prints the median and the spread (min,
+max) over the rounds. Then ``scrub`` on the clean stripe and on the stripe with one whole chunk
+overwritten. Prints one JSON object (also written to ``--out``).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--n", type=int, default=14)
+    ap.add_argument("--matrix", default="vandermonde")
+    ap.add_argument("--cols", type=int, default=107_374_183, help="bytes per chunk")
+    ap.add_argument("--block-bytes", type=int, default=65536)
+    ap.add_argument("--rounds", type=int, default=21, help="alternations of the timed calls")
+    ap.add_argument("--reps", type=int, default=40, help="calls per timed window")
+    ap.add_argument("--scrub-reps", type=int, default=10)
+    ap.add_argument("--out", default=None, help="also write the JSON here")
+    return ap.parse_args(argv)
+
+
+def spread(ms: list[float]) -> dict:
+    return {"median_us": round(statistics.median(ms) * 1e3, 2), "min_us": round(min(ms) * 1e3, 2),
+            "max_us": round(max(ms) * 1e3, 2)}
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    import torch
+
+    from gpu_rscode_amd import ReedSolomon, alloc_rows, flat_rows
+    from gpu_rscode_amd.ops import fill_random_
+
+    if not torch.cuda.is_available():
+        print("scrub_bench.py needs a GPU", file=sys.stderr)
+        return 2
+    k, n, C, bb = args.k, args.n, args.cols, args.block_bytes
+    p = n - k
+    rs = ReedSolomon(k, n, matrix=args.matrix)
+    data = alloc_rows(k, C, "cuda")
+    parity = alloc_rows(p, C, "cuda")
+    fill_random_(flat_rows(data), seed=1)
+    rs.encode(data, parity)
+    stripe = [data[i] for i in range(k)] + [parity[i] for i in range(p)]
+
+    def window(fn, reps) -> float:
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            fn()
+        t.record()
+        t.synchronize()
+        return s.elapsed_time(t) / reps
+
+    def tuned_mask(tune):
+        def call():
+            os.environ["GFRS_TUNE"] = tune
+            try:
+                return rs.syndrome_mask(stripe, bb)
+            finally:
+                del os.environ["GFRS_TUNE"]
+        return call
+
+    general_mask = tuned_mask("scrub_rows=0")
+    base_tune = os.environ.pop("GFRS_TUNE", None)
+    if base_tune:
+        print(f"ignoring GFRS_TUNE={base_tune}", file=sys.stderr)
+    calls = {
+        "syndrome_mask": lambda: rs.syndrome_mask(stripe, bb),
+        "syndrome_mask_multiplied_identity": tuned_mask("scrub_ident=0"),
+        "syndrome_mask_general": general_mask,
+        "verify": lambda: rs.verify(data, parity),
+        "encode": lambda: rs.encode(data, parity),
+    }
+    # the stripe is consistent, by both checks
+    assert not bool(rs.syndrome_mask(stripe, bb).any().item()) and not bool(general_mask().any().item())
+    assert rs.verify(data, parity)
+    for fn in calls.values():  # warm-up: code objects, plans, the allocator's blocks
+        window(fn, 3)
+    times = {name: [] for name in calls}
+    for _ in range(args.rounds):
+        for name, fn in calls.items():
+            times[name].append(window(fn, args.reps))
+    res = {"shape": {"k": k, "n": n, "matrix": args.matrix, "cols": C, "block_bytes": bb},
+           "rounds": args.rounds, "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+    for name, ms in times.items():
+        res[name] = spread(ms)
+    med = {name: statistics.median(ms) for name, ms in times.items()}
+    res["verify_over_syndrome_mask"] = round(med["verify"] / med["syndrome_mask"], 3)
+    res["bytes_predict_verify_over_syndrome_mask"] = round((k + 3 * p) / n, 3)
+    res["syndrome_mask_over_encode"] = round(med["syndrome_mask"] / med["encode"], 3)
+    res["syndrome_mask_TBps"] = round(n * C / (med["syndrome_mask"] * 1e-3) / 1e12, 3)
+    res["encode_TBps"] = round(n * C / (med["encode"] * 1e-3) / 1e12, 3)
+
+    # scrub (both kernels and the one sync): clean, then chunk 3 overwritten
+    rep = rs.scrub(stripe, bb)
+    assert rep.clean
+    res["scrub_clean"] = spread([window(lambda: rs.scrub(stripe, bb), 1) for _ in range(args.scrub_reps)])
+    victim = min(3, n - 1)
+    fill_random_(stripe[victim][: C // 16 * 16], seed=99)
+    rep = rs.scrub(stripe, bb)
+    assert rep.suspects == [victim] and rep.unlocated == 0, (rep.suspects, rep.unlocated)
+    res["scrub_one_bad_chunk"] = spread([window(lambda: rs.scrub(stripe, bb), 1) for _ in range(args.scrub_reps)])
+    res["scrub_one_bad_chunk"]["bad_columns"] = rep.bad_columns
+    healed = rs.heal(stripe, rep)
+    assert healed.clean and rs.verify(data, parity)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
