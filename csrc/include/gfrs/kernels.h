@@ -118,7 +118,9 @@ hipError_t launch_gather_rows(const uint8_t* g, const int* rows, uint8_t* out, i
                               hipStream_t stream);
 
 // ---- int8-MFMA bit-matrix GF-GEMM (csrc/kernels/gf_mfma.hip) ----------------------------------
-// Same contract as launch_gf_gemm but on matrix cores; requires k % 4 == 0 (see kernel notes).
+// Same contract as launch_gf_gemm but on matrix cores, any k; rows 4-byte aligned and col0 a
+// multiple of 4 (a lane loads dwords; hipErrorInvalidValue otherwise, the caller keeps such a
+// start on the v_perm kernel).
 hipError_t launch_gf_gemm_mfma(const void* bitmat, const void* desc, int k, int m, int64_t col0,
                                int64_t ncols, hipStream_t stream);
 size_t mfma_bitmat_bytes(int k, int m);
@@ -128,7 +130,9 @@ size_t mfma_bitmat_bytes(int k, int m);
 // the v_perm kernel (desc must carry the perm tables too).
 // mg_cap bounds the M-tiles (4 output rows each) one block keeps in LDS/accumulators; the bitmat
 // must be built with the same cap. in_stride != 0 promises input row j == input row 0 + j*in_stride
-// (rows of one allocation): DMA addresses are then computed instead of read from a pointer table.
+// (rows of one allocation): DMA addresses are then computed, in 64 bits, instead of read from a
+// pointer table. Any non-zero stride holds: negative (rows listed in reverse) or shorter than the
+// rows (overlapping views). Rows may be longer than 2^32 bytes, and col0 anywhere in them.
 // copies: also write input row j to the descriptor's copy[j] (fused survivor copy of decode).
 hipError_t launch_gf_gemm_fp4(const void* bitmat, const void* desc, int k, int m, int64_t col0,
                               int64_t ncols, int mg_cap, int64_t in_stride, bool copies, hipStream_t stream);
@@ -158,7 +162,10 @@ hipError_t launch_mfma_bitmat(const uint8_t* coeff, int m, int k, void* bitmat,
 // desc: a desc_layout16 descriptor (its v_perm records run the columns past the last 512-byte chunk
 // and any start not 4-byte aligned); bitmat from launch_fp16_bitmat with the same (k, m, mg_cap).
 // Rows 4-byte aligned; col0 / ncols even. K is split into passes (one launch each, later passes XOR
-// into the outputs); copies: fused survivor copy (decode), in_stride as launch_gf_gemm_fp4.
+// into the outputs); copies: fused survivor copy (decode), in_stride as launch_gf_gemm_fp4: the
+// computed-address form (32-bit lane offsets over 8 rows) serves strides of 128 .. 2^28 bytes, any
+// other stride runs on the row pointers like in_stride = 0. Rows longer than 2^32 bytes and any
+// col0 in them are addressed in 64 bits on both forms.
 hipError_t launch_gf_gemm16_fp4(const void* bitmat, const void* desc, int k, int m, int64_t col0, int64_t ncols,
                                 int mg_cap, int64_t in_stride, bool copies, hipStream_t stream);
 // Batched: `batch` stripes whose rows are stripe 0's plus b * in_bstride (inputs) / b * out_bstride

@@ -148,10 +148,11 @@ __device__ __forceinline__ void expand16(i32x4 (&bo)[2], const uint32_t (&x)[4])
   }
 }
 
-// MG: M-tiles (4 output symbol rows each) per block; UNI: input row r at in[0] + r * in_stride (8 *
-// in_stride <= 2^31: a lane's rows sit at 32-bit offsets from the step's first row), else row
-// pointers from the descriptor (columns below 2^32); COPY: fused survivor copies; ACC: XOR into the
-// outputs (passes after the first). nchunks counts whole chunks plus, when tail_bytes > 0, one last
+// MG: M-tiles (4 output symbol rows each) per block; UNI: input row r at in[0] + r * in_stride (128
+// <= in_stride <= 2^28, launch16: a lane's rows sit at 32-bit offsets from the step's first row, 8 *
+// in_stride <= 2^31 = the "reads nothing" offset, and the last live row's 128 wave columns end
+// inside num_records), else row pointers from the descriptor (64-bit addresses: any stride, order
+// and column); COPY: fused survivor copies; ACC: XOR into the outputs (passes after the first). nchunks counts whole chunks plus, when tail_bytes > 0, one last
 // partial chunk of that many bytes (lanes past it load zeros and store nothing).
 //
 // Issue budget. A wave's step is 8 MG MFMAs (32 cycles each); with two waves per SIMD every
@@ -545,8 +546,10 @@ hipError_t launch16(const void* bitmat, const void* desc, int k, int m, int batc
   a.col0 = col0;
   a.fps = full + (tail ? 1 : 0);
   a.nchunks = a.fps * batch;
-  // uniform-stride inputs address rows as the step's first row + 32-bit lane offsets (8 rows)
-  a.in_stride = (copies || in_stride <= 0 || in_stride > (int64_t(1) << 28)) ? 0 : in_stride;
+  // uniform-stride inputs address rows as the step's first row + 32-bit lane offsets (8 rows) inside
+  // num_records = live rows x in_stride: reversed rows, rows more than 2^28 bytes apart and
+  // overlapping rows closer than a wave's columns take the pointer form
+  a.in_stride = (copies || in_stride < kWaveBytes || in_stride > (int64_t(1) << 28)) ? 0 : in_stride;
   a.sink = reinterpret_cast<uint64_t>(bitmat) + bitmat16_matrix_bytes(geo);
   a.tail = tail;
   a.in_bstride = in_bstride;

@@ -378,7 +378,7 @@ class GemmPlan:
                        self.mfma_mg, self.in_stride, self.has_copies, s)
         elif self.engine == "lut" and vec is None and col0 % 16 == 0:
             h.gemm_lut(int(self.desc.data_ptr()), self.k, self.m_pad, col0, ncols, s)
-        elif self.engine == "mfma_i8" and vec is None and col0 % 2 == 0:
+        elif self.engine == "mfma_i8" and vec is None and col0 % 4 == 0:  # (a lane loads dwords)
             h.gemm_mfma(int(self.bitmat.data_ptr()), int(self.desc.data_ptr()), self.k, self.m, col0, ncols, s)
         elif self.bytewise:
             h.gemm(int(self.desc.data_ptr()), self.k, self.m_pad, col0, ncols, True, max_blocks, s)
