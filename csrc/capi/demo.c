@@ -6,7 +6,9 @@
  *      10 lost; 20 of 128 on the wide stripe, whose decoder then runs on the matrix cores);
  *   3. an invalid survivor list (status 2) and a singular one via gfrs_decode_matrix;
  *   4. a wide stripe, k=128 p=32, on the FP4 matrix-core engine;
- *   5. host rows through the streaming pipeline.
+ *   5. host rows through the streaming pipeline;
+ *   6. a partial-stripe write: one native of an encoded stripe overwritten through gfrs_update_*
+ *      (parity updated in place from the changed native alone), compared with a re-encode.
  * Build: make -C csrc capi   (bin/gfrs_capi_demo). Exit 0 = OK, 77 = no GPU visible.
  */
 #include <stdint.h>
@@ -173,6 +175,60 @@ static void host_pipeline(void) {
   printf("host pipeline k=%d p=%d C=%lld OK\n", k, p, (long long)C);
 }
 
+/* 6. overwrite native `j` of an encoded RS(10,14) stripe: the parity rows are updated in place from
+ * old ^ new of that one row, then a second window of it in the delta form */
+static void partial_write(void) {
+  const int k = 10, p = 4, j = 3;
+  const int64_t C = (1 << 20) + 4096 + 17;
+  uint8_t e[40], col[4];
+  CHECK(gfrs_encoding_matrix(GFRS_MATRIX_VANDERMONDE_REF, k, p, e));
+  for (int i = 0; i < p; ++i) col[i] = e[i * k + j]; /* the p x 1 block E[:, j] */
+  uint8_t** data = host_rows(k, C);
+  uint8_t** par = host_rows(p, C);
+  uint8_t** fresh = host_rows(1, C);
+  srand(99);
+  for (int r = 0; r < k; ++r)
+    for (int64_t x = 0; x < C; ++x) data[r][x] = (uint8_t)rand();
+  for (int64_t x = 0; x < C; ++x) fresh[0][x] = (uint8_t)rand();
+  void** d_chunks = dev_rows(k + p, C);
+  void** d_new = dev_rows(1, C);
+  for (int r = 0; r < k; ++r) CHECK(gfrs_copy(d_chunks[r], data[r], (size_t)C));
+  CHECK(gfrs_copy(d_new[0], fresh[0], (size_t)C));
+  gfrs_plan* enc = NULL;
+  CHECK(gfrs_plan_create(&enc, 0, k, p, e, (const void* const*)d_chunks, d_chunks + k, NULL, C, GFRS_ENGINE_VALU));
+  CHECK(gfrs_plan_run(enc, NULL));
+
+  gfrs_update* upd = NULL;
+  CHECK(gfrs_update_create(&upd, 0, 1, p, col, d_chunks + j, (const void* const*)d_new, d_chunks + k, 1));
+  CHECK(gfrs_update_run(upd, 0, C, NULL));
+  CHECK(gfrs_sync(0));
+  memcpy(data[j], fresh[0], (size_t)C);
+  host_gemm(e, p, k, data, par, C); /* the re-encode of the stripe that holds the new native */
+  EXPECT(rows_equal_device(d_chunks + j, fresh, 1, C), "update MISMATCH: native not overwritten");
+  EXPECT(rows_equal_device(d_chunks + k, par, p, C), "update MISMATCH: parity differs from a re-encode");
+  gfrs_update_destroy(upd);
+
+  /* delta form over a window: the parity node receives old ^ new of columns [c0, c0 + nc) only */
+  const int64_t c0 = 4099, nc = 70001;
+  for (int64_t x = 0; x < C; ++x) fresh[0][x] = (uint8_t)(x >= c0 && x < c0 + nc ? rand() | 1 : 0);
+  CHECK(gfrs_copy(d_new[0], fresh[0], (size_t)C));
+  CHECK(gfrs_update_create(&upd, 0, 1, p, col, d_new, NULL, d_chunks + k, 0));
+  CHECK(gfrs_update_run(upd, c0, nc, NULL));
+  CHECK(gfrs_sync(0));
+  for (int64_t x = c0; x < c0 + nc; ++x) data[j][x] ^= fresh[0][x];
+  host_gemm(e, p, k, data, par, C);
+  EXPECT(rows_equal_device(d_chunks + k, par, p, C), "update MISMATCH: delta form");
+  EXPECT(gfrs_update_run(upd, -1, 16, NULL) == GFRS_EINVAL, "update MISMATCH: negative col0 accepted");
+  gfrs_update_destroy(upd);
+  gfrs_plan_destroy(enc);
+  free_rows(d_chunks, NULL, k + p);
+  free_rows(d_new, fresh, 1);
+  free_rows(NULL, data, k);
+  free_rows(NULL, par, p);
+  printf("partial write k=%d p=%d C=%lld: update of native %d (write, then a delta window) equals a re-encode OK\n", k,
+         p, (long long)C, j);
+}
+
 int main(void) {
   gf_init();
   printf("gfrs C API v%d, %d device(s)\n", gfrs_api_version(), gfrs_device_count());
@@ -180,6 +236,7 @@ int main(void) {
   stripe_round_trip(10, 4, (1 << 20) + 4096 + 17, GFRS_ENGINE_VALU, 3);
   stripe_round_trip(128, 32, (1 << 18) + 256 * 3 + 96, GFRS_ENGINE_MFMA, 20);
   host_pipeline();
+  partial_write();
   CHECK(gfrs_release());
   printf("capi_demo OK\n");
   return 0;

@@ -225,6 +225,20 @@ struct gfrs_plan16 {
   }
 };
 
+// ---- in-place parity update -------------------------------------------------------------------
+// One descriptor per pass of at most kUpdateMaxD changed rows (XOR accumulation makes the passes
+// independent); the row addresses are kept to check each run's byte ranges for overlap.
+struct gfrs_update {
+  struct Pass {
+    int d = 0;
+    DevBuf desc;
+  };
+  int device = 0, d = 0, p = 0, m_pad = 0;
+  bool pairs = false, store_new = false, bytewise = false;
+  std::vector<uint64_t> first, second, parity;
+  std::vector<std::unique_ptr<Pass>> passes;
+};
+
 // ---- decoder --------------------------------------------------------------------------------
 struct gfrs_decoder {
   int k = 0, n = 0, e = 0;
@@ -426,6 +440,85 @@ void gfrs_plan_destroy(gfrs_plan* p) {
   if (!p) return;
   DeviceGuard g(p->device, DeviceGuard::NoThrow{});
   delete p;
+}
+
+int gfrs_update_create(gfrs_update** upd, int device, int d, int p, const uint8_t* coeff, void* const* old_or_delta,
+                       const void* const* new_rows, void* const* parity, int store_new) {
+  return guarded([&] {
+    need(upd && coeff && old_or_delta && parity, "update_create: upd, coeff, old_or_delta and parity are required");
+    need(d >= 1 && d <= 256 && p >= 1 && p <= 255, "update_create: 1 <= d <= 256 and 1 <= p <= 255");
+    need(!store_new || new_rows, "update_create: store_new needs new_rows (the pair form)");
+    auto u = std::make_unique<gfrs_update>();
+    u->device = device;
+    u->d = d;
+    u->p = p;
+    u->m_pad = gfrs::pad_m(p);
+    u->pairs = new_rows != nullptr;
+    u->store_new = store_new != 0;
+    u->first = addrs(const_cast<const void* const*>(old_or_delta), d);
+    u->parity = addrs(const_cast<const void* const*>(parity), p);
+    if (new_rows) u->second = addrs(new_rows, d);
+    std::vector<uint64_t> all(u->parity);
+    all.insert(all.end(), u->first.begin(), u->first.end());
+    all.insert(all.end(), u->second.begin(), u->second.end());
+    for (uint64_t a : all) need(a != 0, "update_create: null row");
+    // rows that start at one address overlap whatever the window (gfrs_update_run checks the ranges)
+    for (size_t i = 0; i < u->parity.size(); ++i)
+      for (size_t j = i + 1; j < all.size(); ++j)
+        need(all[i] != all[j], "update_create: a parity row is also another row");
+    for (uint64_t a : u->first)
+      for (uint64_t b : u->second) need(a != b, "update_create: a new row is also an old row");
+    u->bytewise = std::any_of(all.begin(), all.end(), [](uint64_t a) { return a % 16 != 0; });
+    DeviceGuard g(device);
+    for (int t0 = 0; t0 < d; t0 += gfrs::kUpdateMaxD) {
+      const int dd = std::min(d - t0, gfrs::kUpdateMaxD);
+      gfrs::Mat c(size_t(p) * dd);  // E[:, changed[t0 .. t0 + dd)]
+      for (int i = 0; i < p; ++i) std::copy_n(coeff + size_t(i) * d + t0, dd, c.begin() + size_t(i) * dd);
+      const std::vector<uint64_t> in(u->first.begin() + t0, u->first.begin() + t0 + dd);
+      std::vector<uint64_t> cp;
+      if (new_rows) cp.assign(u->second.begin() + t0, u->second.begin() + t0 + dd);
+      const std::vector<uint8_t> host = gfrs::build_desc(dd, p, in, cp, u->parity, c);
+      auto pass = std::make_unique<gfrs_update::Pass>();
+      pass->d = dd;
+      pass->desc.alloc(host.size());
+      hip_check(hipMemcpy(pass->desc.p, host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy desc");
+      u->passes.push_back(std::move(pass));
+    }
+    *upd = u.release();
+  });
+}
+
+int gfrs_update_run(gfrs_update* u, int64_t col0, int64_t ncols, void* stream) {
+  return guarded([&] {
+    need(u != nullptr, "update_run: null update");
+    need(col0 >= 0 && ncols >= 0, "update_run: col0 and ncols must be >= 0");
+    if (ncols == 0) return;
+    // the kernel works in place, lane by lane: a parity row's window must not overlap any other
+    // row's, nor a new row's an old row's
+    const uint64_t len = uint64_t(ncols);
+    auto overlap = [len](uint64_t a, uint64_t b) { return a < b + len && b < a + len; };
+    std::vector<uint64_t> others(u->first);
+    others.insert(others.end(), u->second.begin(), u->second.end());
+    for (size_t i = 0; i < u->parity.size(); ++i) {
+      for (size_t j = i + 1; j < u->parity.size(); ++j)
+        need(!overlap(u->parity[i], u->parity[j]), "update_run: two parity rows overlap in this window");
+      for (uint64_t b : others) need(!overlap(u->parity[i], b), "update_run: a parity row overlaps another row");
+    }
+    for (uint64_t a : u->first)
+      for (uint64_t b : u->second) need(!overlap(a, b), "update_run: a new row overlaps an old row");
+    DeviceGuard g(u->device);
+    const bool bytewise = u->bytewise || col0 % 16 != 0;
+    for (const auto& pass : u->passes)
+      hip_check(gfrs::launch_gf_update(pass->desc.p, pass->d, u->m_pad, col0, ncols, u->pairs, u->store_new, bytewise,
+                                       as_stream(stream)),
+                "gf_update");
+  });
+}
+
+void gfrs_update_destroy(gfrs_update* u) {
+  if (!u) return;
+  DeviceGuard g(u->device, DeviceGuard::NoThrow{});
+  delete u;
 }
 
 int gfrs_decoder_create(gfrs_decoder** dec, int device, int k, int p, const uint8_t* e, void* const* chunks,

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define GFRS_API_VERSION 3
+#define GFRS_API_VERSION 4
 
 enum {
   GFRS_OK = 0,
@@ -83,6 +83,22 @@ int gfrs_plan16_create(gfrs_plan16** plan, int device, int k, int m, const uint1
 int gfrs_plan16_run(gfrs_plan16* plan, void* stream);
 int gfrs_plan16_engine(const gfrs_plan16* plan); /* GFRS_ENGINE_VALU or GFRS_ENGINE_MFMA */
 void gfrs_plan16_destroy(gfrs_plan16* plan);
+
+/* ---- in-place parity update for partial-stripe writes (API version 4) ------------------------- */
+/* When d natives of a stripe change, every parity row moves by coeff[i][t] * (old[t] ^ new[t]),
+ * coeff = the columns of the p x k encoding matrix of the changed natives (p x d row-major, host):
+ * the update reads the changed natives and the parity rows only, not the other k - d natives.
+ * old_or_delta: d device rows; new_rows: d device rows (the pair form: the delta is formed on the
+ * fly) or NULL (the delta form: old_or_delta holds old ^ new); parity: p device rows, updated in
+ * place. store_new (pair form only): old_or_delta[t] is also overwritten with new_rows[t] in the
+ * same pass, so a write into a stripe is one call. 1 <= d <= 256 (more than 8 run as passes of 8),
+ * 1 <= p <= 255. run covers byte columns [col0, col0 + ncols) of every row, asynchronously on
+ * stream; there no parity row may overlap another row, nor a new row an old one (GFRS_EINVAL). */
+typedef struct gfrs_update gfrs_update;
+int gfrs_update_create(gfrs_update** upd, int device, int d, int p, const uint8_t* coeff, void* const* old_or_delta,
+                       const void* const* new_rows, void* const* parity, int store_new);
+int gfrs_update_run(gfrs_update* upd, int64_t col0, int64_t ncols, void* stream);
+void gfrs_update_destroy(gfrs_update* upd);
 
 /* ---- decoder with a device-resident erasure pattern ------------------------------------------ */
 /* chunks: the stripe's n = k + p device rows (natives, then parity), out: k device rows, all

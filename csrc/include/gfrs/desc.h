@@ -13,6 +13,11 @@
 //   [.., +8k)             copy_ptr[k]    (0 = no copy)
 //   [.., +8*m_pad)        out_ptr[m_pad] (0 = padding row, never stored)
 //   align 32, [.., +32*k*m_pad)   PermTable tab[k][m_pad]
+//
+// The in-place parity update (csrc/kernels/gf_update.hip) reuses the record as desc_layout(d, m_pad)
+// for d changed natives and p parity rows: in_ptr[t] = old_t (or delta_t in the delta form),
+// copy_ptr[t] = new_t (0 in the delta form; read, not written), out_ptr[i] = parity_i (read and
+// written in place; 0 = padding row, skipped), tab[t][i] = the map of E[i][changed[t]].
 #pragma once
 
 #include <cstdint>

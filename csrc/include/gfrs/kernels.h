@@ -68,6 +68,25 @@ hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool 
                             const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
                             hipStream_t stream);
 
+// ---- in-place parity update (csrc/kernels/gf_update.hip) ---------------------------------------
+// The parity of a stripe in which d natives changed, from those natives and the parity rows alone:
+// over byte columns [col0, col0 + ncols), parity_i ^= XOR_t L[i][t](x_t) in place, with x_t =
+// old_t ^ new_t (pairs) or x_t = delta_t (!pairs); store_new (pairs only) also overwrites old_t with
+// new_t in the same pass (a write into an n-row stripe). desc: a desc_layout(d, m_pad) descriptor
+// (gfrs/desc.h documents the reuse): in_ptr[t] = old_t or delta_t, copy_ptr[t] = new_t (0 in the
+// delta form), out_ptr[i] = parity_i (0 = padding, skipped), tables of E[:, changed] (p x d), m_pad =
+// pad_m(p) with any p in [1, 255]. One launch, one lane per 16-byte group walking every parity row;
+// the ragged tail runs on extra lanes of the same launch. force_bytewise (rows not 16-byte aligned)
+// or col0 % 16 != 0 takes the byte-per-lane form, the rule of launch_gf_gemm. Rows may be longer
+// than 2^32 bytes. The parity rows must not overlap each other or any other row, and new_t must
+// not overlap old_t: the read-modify-write is per lane. hipErrorInvalidValue, and nothing launched,
+// for d outside [1, kUpdateMaxD] (callers split a longer list into passes: XOR accumulation makes
+// them independent), an m_pad that pad_m does not produce, col0 < 0, ncols < 0, store_new without
+// pairs, or a null desc; ncols == 0 succeeds without a launch.
+constexpr int kUpdateMaxD = 8;  // 32 VGPRs of deltas per lane
+hipError_t launch_gf_update(const void* desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs,
+                            bool store_new, bool force_bytewise, hipStream_t stream);
+
 // ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip) ---------------------------------------
 // Inverts `batch` n x n matrices (row-major, contiguous) with row pivoting, one workgroup each,
 // [A|I] resident in LDS. status[b] = 0 ok, 1 singular. n <= 256.

@@ -338,3 +338,15 @@ def scrub_oracle(h: np.ndarray, rows, block_bytes: int = 65536):
         votes[j] = int(match.sum())
         pending &= ~match
     return mask, votes, int(pending.sum()), bad_columns
+
+
+# ---- partial-stripe writes: the delta identity -----------------------------------------------------
+def update_oracle(e: np.ndarray, parity, changed, old, new) -> np.ndarray:
+    """Plain numpy parity update over GF(2^8): the parity rows of the stripe in which natives
+    ``changed[t]`` hold ``new[t]`` instead of ``old[t]``, from the old parity alone:
+    ``parity ^ E[:, changed] . (old ^ new)``. ``e`` is the p x k encoding block; ``parity`` [p, C],
+    ``old`` and ``new`` [d, C]. Returns a new array."""
+    e = np.asarray(e, dtype=np.uint8)
+    parity = np.asarray(parity, dtype=np.uint8)
+    delta = np.asarray(old, dtype=np.uint8) ^ np.asarray(new, dtype=np.uint8)
+    return parity ^ GF256.gemm(e[:, [int(j) for j in changed]], delta)

@@ -20,11 +20,12 @@ import torch
 
 from .. import gf
 from .._native import cpu, hip
-from ..ops.gemm import Gemm16Plan, GemmPlan, _rows
+from ..ops.gemm import Gemm16Plan, GemmPlan, _null, _rows
 from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, decode_system_into_plan
 from ..ops.matrix import decode_matrix, encoding_matrix
 from ..ops.scrub import (MAX_LOCATE_P, ScrubPlan, ScrubReport, check_block_bytes, cpu_scrub, make_report,
                          stripe_rows)
+from ..ops.update import UpdatePlan, _window, check_overlap, cpu_update
 
 PITCH = 256
 
@@ -166,6 +167,7 @@ class ReedSolomon:
         self._g16_bytes: tuple | None = None  # (the G it was made from, its uint16 bytes)
         self.G = np.vstack([np.eye(k, dtype=dt), self.E]).astype(dt)
         self._plans = _PlanCache()
+        self._upd_keys = _PlanCache()  # arguments of a repeated update call -> its key in _plans
         self._g_dev: dict = {}  # (device, id(G)) -> G on device, for the on-device decode system
 
     @property
@@ -183,6 +185,7 @@ class ReedSolomon:
         self._g16_bytes = None
         if hasattr(self, "_plans"):  # (absent during __init__)
             self._plans.clear()
+            self._upd_keys.clear()
             self._g_dev.clear()
 
     @property
@@ -626,6 +629,124 @@ class ReedSolomon:
                 f"suspects {report.suspects}: not repairable from p={self.p} parity chunks")
         self.reconstruct(stripe, erased=report.suspects)
         return self.scrub(stripe)
+
+    # ---- partial-stripe writes ----------------------------------------------------------------
+    def _update_rows(self, what: str, changed, parity, first, second):
+        """Validated (changed, parity rows, first rows, second rows, shortest row, device)."""
+        changed = [int(j) for j in changed]
+        if not 1 <= len(changed) <= self.k or len(set(changed)) != len(changed) or min(changed) < 0 \
+                or max(changed) >= self.k:
+            raise ValueError(f"{what}: changed must be 1..k distinct native ids in [0, {self.k}), got {changed}")
+        par, first = _rows(parity), _rows(first)
+        second = None if second is None else _rows(second)
+        if len(par) != self.p:
+            raise ValueError(f"{what}: expected p={self.p} parity rows, got {len(par)}")
+        if len(first) != len(changed) or (second is not None and len(second) != len(changed)):
+            raise ValueError(f"{what}: expected {len(changed)} rows per changed native")
+        rows = par + first + (second or [])
+        for r in rows:
+            if not isinstance(r, torch.Tensor) or r.dtype != torch.uint8:
+                raise ValueError(f"{what}: rows must be uint8 tensors")
+            if r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
+                raise ValueError(f"{what}: rows must be contiguous 1-D byte rows")
+            if r.device != rows[0].device:
+                raise ValueError(f"{what}: all rows must live on one device ({rows[0].device} vs {r.device})")
+        return changed, par, first, second, min(r.numel() for r in rows), rows[0].device
+
+    @staticmethod
+    def _arg_id(x):
+        if isinstance(x, torch.Tensor):
+            return (x.data_ptr(), x.shape, x.stride(), x.dtype)
+        return None if x is None else tuple((r.data_ptr(), r.numel()) for r in x)
+
+    def _update_again(self, form, changed, args, col0, ncols, stream):
+        """A repeated call on the same CUDA buffers: two dict lookups instead of per-row views,
+        checks and the key of p + 2 d rows (an update of a few MiB per row is launch-bound, as
+        :meth:`encode`). Returns the id of the arguments, or None after running the cached plan."""
+        try:
+            ident = (form, tuple(changed)) + tuple(self._arg_id(a) for a in args)
+            key = self._upd_keys.get(ident)
+        except (AttributeError, TypeError):  # not tensors: the full path says what is wrong
+            return False
+        plan = self._plans.get(key) if key is not None else None
+        if plan is None:
+            return ident
+        plan.run(stream, col0, ncols)
+        return None
+
+    def _update(self, what, form, changed, par, first, second, limit, dev, col0, ncols, stream, ident=False):
+        col0, ncols = _window(col0, ncols, limit)
+        store_new = form == "write"
+        check_overlap(par, first, second, store_new)
+        if dev.type == "cuda":
+            if self.wide:
+                raise NotImplementedError(f"{what} on the GPU is implemented for field='gf256' and 'gf16', "
+                                          f"not {self.field!r} (CPU tensors work)")
+            if self.p == 0:
+                if store_new:
+                    with torch.cuda.stream(stream) if stream is not None else _null():
+                        for a, b in zip(first, second):
+                            a[col0: col0 + ncols].copy_(b[col0: col0 + ncols], non_blocking=True)
+                return
+            key = self._key(("upd", form, tuple(changed)), par, first, second or [])
+            plan = self._plans.get(key)
+            if plan is None:
+                coeff = self.E[:, changed]
+                maps = self._maps(coeff)
+                plan = self._plans[key] = UpdatePlan(par, first, second, None if maps is not None else coeff,
+                                                     maps=maps, store_new=store_new)
+            if ident:
+                self._upd_keys[ident] = key
+            plan.run(stream, col0, ncols)
+            return
+        if self.wide and (col0 | ncols) & 1:
+            raise ValueError("GF(2^16) rows hold 16-bit symbols: col0 and ncols must be even byte counts")
+        cpu_update(self.E[:, changed], par, first, second, col0, ncols, self._cpu_gemm, store_new)
+
+    def update(self, parity, changed: Sequence[int], old, new, col0: int = 0, ncols: int | None = None,
+               stream: torch.cuda.Stream | None = None):
+        """Partial-stripe write, parity side: over byte columns ``[col0, col0 + ncols)`` ``parity``
+        (p rows, in place) becomes the parity of the stripe in which natives ``changed[t]`` hold
+        ``new[t]`` instead of ``old[t]``: ``parity_i ^= E[i][changed[t]] . (old[t] ^ new[t])``. Only
+        the changed natives and the parity rows are read: ``2 d + 2 p`` rows move, where a re-encode
+        moves ``k + p``. ``changed``: 1..k distinct native ids, any order; ``old`` / ``new``: [d, C]
+        tensors or lists of d rows, left unchanged. ``ncols`` defaults to the shortest row minus
+        ``col0``; bytes outside the window are never touched. No parity row may overlap another row
+        and no ``new`` row an ``old`` row (``ValueError``). Returns ``parity``."""
+        ident = self._update_again("pair", changed, (parity, old, new), col0, ncols, stream)
+        if ident is None:
+            return parity
+        ch, par, first, second, limit, dev = self._update_rows("update", changed, parity, old, new)
+        self._update("update", "pair", ch, par, first, second, limit, dev, col0, ncols, stream, ident)
+        return parity
+
+    def update_delta(self, parity, changed: Sequence[int], delta, col0: int = 0, ncols: int | None = None,
+                     stream: torch.cuda.Stream | None = None):
+        """:meth:`update` from ``delta[t] = old[t] ^ new[t]``, what a data node ships to a parity
+        node: ``d + 2 p`` rows move. Returns ``parity``."""
+        ident = self._update_again("delta", changed, (parity, delta), col0, ncols, stream)
+        if ident is None:
+            return parity
+        ch, par, first, _, limit, dev = self._update_rows("update_delta", changed, parity, delta, None)
+        self._update("update_delta", "delta", ch, par, first, None, limit, dev, col0, ncols, stream, ident)
+        return parity
+
+    def write(self, stripe, changed: Sequence[int], new, col0: int = 0, ncols: int | None = None,
+              stream: torch.cuda.Stream | None = None):
+        """Partial-stripe write into an n-row stripe (natives first, as for :meth:`reconstruct`): over
+        byte columns ``[col0, col0 + ncols)`` natives ``changed[t]`` are overwritten with ``new[t]``
+        and the parity rows updated, in one pass. ``new`` must not overlap the stripe. Returns
+        ``stripe``."""
+        ident = self._update_again("write", changed, (stripe, new), col0, ncols, stream)
+        if ident is None:
+            return stripe
+        rows = _rows(stripe)
+        if len(rows) != self.n:
+            raise ValueError(f"stripe must have n={self.n} rows")
+        old = [rows[int(j)] for j in changed if 0 <= int(j) < self.k]
+        ch, par, first, second, limit, dev = self._update_rows("write", changed, rows[self.k:], old, new)
+        self._update("write", "write", ch, par, first, second, limit, dev, col0, ncols, stream, ident)
+        return stripe
 
     def verify(self, data, parity) -> bool:
         """True when ``parity`` is the encoding of ``data`` (recomputes and compares)."""
