@@ -67,6 +67,20 @@ hipError_t launch_gf_syndrome(const void* desc, int n, int m_pad, int ident, int
 hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
                             const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
                             hipStream_t stream);
+// Batched forms (small-object scrubbing: one launch for many stripes, grid.y = stripe): `batch` >= 1
+// stripes of identical shape under one H. desc built with desc_layout(n, m_pad, batch): stripe b's
+// rows are in_ptr[b * n + j], the tables are shared. mask holds batch rows of nmask = ceil(ncols /
+// block_bytes) words (stripe b's at mask + b * nmask), zeroed here by one memset; counts holds batch
+// rows of n + 2 (stripe b's at counts + b * (n + 2)), likewise. Every form of the single launchers
+// runs per stripe (for (4, 6) and (10, 14) with ident == p the rows-in-flight kernel), and a
+// consistent batch stores nothing but the memset. More than 65535 stripes (the grid.y limit) run as
+// several launches of at most that many each. hipErrorInvalidValue with nothing written for
+// batch < 1, a null desc and whatever the single launchers refuse.
+hipError_t launch_gf_syndrome_batched(const void* desc, int n, int m_pad, int ident, int batch, int64_t ncols,
+                                      bool force_bytewise, int64_t block_bytes, int32_t* mask, hipStream_t stream);
+hipError_t launch_gf_locate_batched(const void* desc, int n, int p, int batch, int64_t ncols, bool force_bytewise,
+                                    int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
+                                    uint64_t* counts, hipStream_t stream);
 
 // ---- in-place parity update (csrc/kernels/gf_update.hip) ---------------------------------------
 // The parity of a stripe in which d natives changed, from those natives and the parity rows alone:

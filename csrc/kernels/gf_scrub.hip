@@ -15,6 +15,10 @@
 //     chunk k + i; several blame the native j with s == e . H[:, j], e = s_r / H[r][j], r = column
 //     j's pivot row; anything else is unlocated. Counts go through an LDS histogram per workgroup
 //     and one 64-bit atomic add per nonzero bin.
+// Both have a batched form (template flag BATCH, grid.y = stripe) over a desc_layout(n, m_pad, batch)
+// descriptor, for scrubbing many small stripes in one launch: stripe b reads its own row pointers and
+// writes its own mask and counts rows; the tables of H are shared. The single-stripe launchers run
+// the BATCH = false instantiations, which the flag leaves exactly as they were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -98,12 +102,25 @@ __device__ __forceinline__ int64_t wave_block(int64_t g0, int64_t ngroups, int b
   return ((g0 < ngroups ? g0 : ngroups) * 16) >> bshift;
 }
 
+// Stripe b = blockIdx.y of a batched launch (gf_gemm.hip's stripe()): its own n row pointers and its
+// own row of ceil(ncols / block_bytes) mask words, both offsets formed in 64 bits. A wave never spans
+// two stripes, so everything wave_or and wave_block assume holds within each.
+template <bool BATCH>
+__device__ __forceinline__ void stripe(DescView& d, int n, int*& mask, int64_t ncols, int bshift) {
+  if constexpr (BATCH) {
+    const uint64_t b = blockIdx.y;
+    d.in += b * uint64_t(n);
+    mask += b * uint64_t((ncols + (int64_t(1) << bshift) - 1) >> bshift);
+  }
+}
+
 // General form: any n, two rows in flight, grid-stride over column blocks (gf_gemm_vec_kernel with
 // V = 1, PF = 2, non-temporal loads, no copies and no stores).
-template <int MT>
+template <int MT, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_syndrome_vec_kernel(DescView d, int n, int m_pad, int ntiles,
                                                                  int64_t ngroups, int64_t nblk, int64_t ncb, int tail,
                                                                  int* mask, int bshift) {
+  stripe<BATCH>(d, n, mask, ngroups * 16 + tail, bshift);
   const TileMap tm = map_block(ntiles);
   if (tm.cb0 >= ncb) return;
   const int i0 = tm.tile * MT;
@@ -168,10 +185,11 @@ __global__ __launch_bounds__(kBlock) void gf_syndrome_vec_kernel(DescView d, int
 // IDENT: the last MT columns of H are the identity (H = [E | I_p], p = MT), so parity row i is
 // XORed into syndrome row i as it is instead of going through the tables of 0 and 1: the multiplies
 // of an encode (k x p) are left, not n x p.
-template <int MT, int N, bool IDENT>
+template <int MT, int N, bool IDENT, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_syndrome_rows_kernel(DescView d, int n_tail, int m_pad, int ntiles,
                                                                   int64_t ngroups, int tail, int* mask, int bshift) {
   constexpr int K = IDENT ? N - MT : N;  // rows that are multiplied
+  stripe<BATCH>(d, N, mask, ngroups * 16 + tail, bshift);
   const TileMap tm = map_block(ntiles);
   const int i0 = sgpr_int(tm.tile * MT);
   const int64_t g = tm.cb0 * kBlock + threadIdx.x;
@@ -235,10 +253,11 @@ __global__ __launch_bounds__(kBlock) void gf_syndrome_rows_kernel(DescView d, in
 
 // Byte form: one lane per byte column, rows of any alignment. A wave's 64 columns share a mask word
 // (block_bytes is a multiple of 64).
-template <int MT>
+template <int MT, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_syndrome_byte_kernel(DescView d, int n, int m_pad, int ntiles,
                                                                   int64_t ncols, int64_t nblk, int64_t ncb, int* mask,
                                                                   int bshift) {
+  stripe<BATCH>(d, n, mask, ncols, bshift);
   const TileMap tm = map_block(ntiles);
   if (tm.cb0 >= ncb) return;
   const int i0 = tm.tile * MT;
@@ -309,10 +328,18 @@ __device__ __forceinline__ void classify(const LocLds& l, uint32_t* hist, const 
   ++unl;
 }
 
-template <int MT>
+// BATCH: grid.y = stripe; the stripe's own rows, mask row and n + 2 counts (histogram and totals
+// are per stripe). A workgroup whose stripe's mask word is zero still leaves before any barrier.
+template <int MT, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_locate_kernel(DescView d, int n, int p, int64_t ncols, int bshift,
                                                            int span_shift, const int* mask, const uint8_t* loc,
                                                            int locatable, int bytewise, unsigned long long* counts) {
+  if constexpr (BATCH) {
+    const uint64_t b = blockIdx.y;
+    d.in += b * uint64_t(n);
+    mask += b * uint64_t((ncols + (int64_t(1) << bshift) - 1) >> bshift);
+    counts += b * uint64_t(n + 2);
+  }
   const int64_t base = int64_t(blockIdx.x) << span_shift;
   if (mask[base >> bshift] == 0) return;  // (uniform: the whole workgroup leaves before any barrier)
   __shared__ LocLds l;
@@ -395,28 +422,30 @@ inline int log2_exact(int64_t v) {
 // trailing identity columns of H, and with ident == MT the parity rows skip the multiplies.
 // GFRS_TUNE=scrub_rows=0 keeps every launch on the general form, scrub_ident=0 multiplies the
 // identity columns too (A/B measurements, profiles/scrub).
-template <int MT, int N>
-void launch_rows_n(const DescView& d, int m_pad, int ident, const Grid& g, int64_t ngroups, int tail, int* mask,
-                   int bshift, hipStream_t stream) {
+// In all of these BATCH picks the batched instantiation and `batch` is grid.y (1 when !BATCH).
+template <int MT, int N, bool BATCH>
+void launch_rows_n(const DescView& d, int m_pad, int ident, const Grid& g, unsigned batch, int64_t ngroups, int tail,
+                   int* mask, int bshift, hipStream_t stream) {
+  const dim3 grid(g.blocks, batch);
   if (ident == MT && tune_int("scrub_ident", 1) != 0)
-    gf_syndrome_rows_kernel<MT, N, true><<<g.blocks, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
+    gf_syndrome_rows_kernel<MT, N, true, BATCH><<<grid, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
   else
-    gf_syndrome_rows_kernel<MT, N, false><<<g.blocks, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
+    gf_syndrome_rows_kernel<MT, N, false, BATCH><<<grid, kBlock, 0, stream>>>(d, N, m_pad, 1, ngroups, tail, mask, bshift);
 }
 
-template <int MT>
-bool launch_rows(const DescView& d, int n, int m_pad, int ident, const Grid& g, int64_t ngroups, int tail, int* mask,
-                 int bshift, hipStream_t stream) {
+template <int MT, bool BATCH>
+bool launch_rows(const DescView& d, int n, int m_pad, int ident, const Grid& g, unsigned batch, int64_t ngroups,
+                 int tail, int* mask, int bshift, hipStream_t stream) {
   if (m_pad != MT || g.ncb < g.nblk || tune_int("scrub_rows", 1) == 0) return false;
   if constexpr (MT == 2) {
     if (n == 6) {
-      launch_rows_n<2, 6>(d, m_pad, ident, g, ngroups, tail, mask, bshift, stream);
+      launch_rows_n<2, 6, BATCH>(d, m_pad, ident, g, batch, ngroups, tail, mask, bshift, stream);
       return true;
     }
   }
   if constexpr (MT == 4) {
     if (n == 14) {
-      launch_rows_n<4, 14>(d, m_pad, ident, g, ngroups, tail, mask, bshift, stream);
+      launch_rows_n<4, 14, BATCH>(d, m_pad, ident, g, batch, ngroups, tail, mask, bshift, stream);
       return true;
     }
   }
@@ -427,6 +456,52 @@ bool scrub_args_ok(int n, int m_pad, int64_t ncols, int64_t block_bytes) {
   return n >= 1 && n <= 256 && m_pad >= 1 && m_pad % tile_for(m_pad) == 0 && ncols >= 0 && block_bytes >= 4096 &&
          log2_exact(block_bytes) > 0;
 }
+
+// One syndrome launch over `batch` stripes (grid.y); `d` and `mask` are those of the first of them.
+template <bool BATCH>
+hipError_t syndrome_launch(const DescView& d, int n, int m_pad, int ident, unsigned batch, int64_t ncols,
+                           bool force_bytewise, int bshift, int* mask, hipStream_t stream) {
+  return dispatch_tile(tile_for(m_pad), [&](auto mt) -> hipError_t {
+    constexpr int MT = decltype(mt)::value;
+    const int ntiles = m_pad / MT;
+    if (force_bytewise) {
+      const Grid g = make_grid(ncols, ntiles);
+      gf_syndrome_byte_kernel<MT, BATCH>
+          <<<dim3(g.blocks, batch), kBlock, 0, stream>>>(d, n, m_pad, ntiles, ncols, g.nblk, g.ncb, mask, bshift);
+      return hipGetLastError();
+    }
+    const int64_t ngroups = ncols / 16;
+    const int tail = int(ncols % 16);
+    const Grid g = make_grid(ngroups + tail, ntiles);  // one extra lane per ragged tail byte
+    if (!launch_rows<MT, BATCH>(d, n, m_pad, ident, g, batch, ngroups, tail, mask, bshift, stream))
+      gf_syndrome_vec_kernel<MT, BATCH><<<dim3(g.blocks, batch), kBlock, 0, stream>>>(d, n, m_pad, ntiles, ngroups,
+                                                                                      g.nblk, g.ncb, tail, mask, bshift);
+    return hipGetLastError();
+  });
+}
+
+template <bool BATCH>
+hipError_t locate_launch(const DescView& d, int n, int p, unsigned batch, int64_t ncols, bool force_bytewise,
+                         int bshift, const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
+                         hipStream_t stream) {
+  const int span_shift = std::min(bshift, kLocSpanShift);
+  const int64_t nwg = (ncols + (int64_t(1) << span_shift) - 1) >> span_shift;
+  return dispatch_tile(pad_m(p), [&](auto mt) -> hipError_t {
+    constexpr int MT = decltype(mt)::value;
+    gf_locate_kernel<MT, BATCH><<<dim3(unsigned(nwg), batch), kBlock, 0, stream>>>(
+        d, n, p, ncols, bshift, span_shift, mask, loc, locatable ? 1 : 0, force_bytewise ? 1 : 0,
+        reinterpret_cast<unsigned long long*>(counts));
+    return hipGetLastError();
+  });
+}
+
+bool locate_args_ok(int n, int p, int64_t ncols, int64_t block_bytes) {
+  if (p < 1 || p > 16 || p >= n || !scrub_args_ok(n, pad_m(p), ncols, block_bytes)) return false;
+  const int span_shift = std::min(log2_exact(block_bytes), kLocSpanShift);
+  return ((ncols + (int64_t(1) << span_shift) - 1) >> span_shift) <= int64_t(INT32_MAX);
+}
+
+constexpr int kMaxGridY = 65535;  // stripes per launch, as launch_gf_gemm_batched
 
 }  // namespace
 
@@ -439,44 +514,56 @@ hipError_t launch_gf_syndrome(const void* desc, int n, int m_pad, int ident, int
   const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
   hipError_t e = hipMemsetAsync(mask, 0, size_t(nmask) * sizeof(int32_t), stream);
   if (e != hipSuccess) return e;
-  const DescView d = view(desc, n, m_pad);
-  return dispatch_tile(tile_for(m_pad), [&](auto mt) -> hipError_t {
-    constexpr int MT = decltype(mt)::value;
-    const int ntiles = m_pad / MT;
-    if (force_bytewise) {
-      const Grid g = make_grid(ncols, ntiles);
-      gf_syndrome_byte_kernel<MT><<<g.blocks, kBlock, 0, stream>>>(d, n, m_pad, ntiles, ncols, g.nblk, g.ncb, mask, bshift);
-      return hipGetLastError();
-    }
-    const int64_t ngroups = ncols / 16;
-    const int tail = int(ncols % 16);
-    const Grid g = make_grid(ngroups + tail, ntiles);  // one extra lane per ragged tail byte
-    if (!launch_rows<MT>(d, n, m_pad, ident, g, ngroups, tail, mask, bshift, stream))
-      gf_syndrome_vec_kernel<MT>
-          <<<g.blocks, kBlock, 0, stream>>>(d, n, m_pad, ntiles, ngroups, g.nblk, g.ncb, tail, mask, bshift);
-    return hipGetLastError();
-  });
+  return syndrome_launch<false>(view(desc, n, m_pad), n, m_pad, ident, 1, ncols, force_bytewise, bshift, mask, stream);
+}
+
+hipError_t launch_gf_syndrome_batched(const void* desc, int n, int m_pad, int ident, int batch, int64_t ncols,
+                                      bool force_bytewise, int64_t block_bytes, int32_t* mask, hipStream_t stream) {
+  if (batch < 1 || !desc || !scrub_args_ok(n, m_pad, ncols, block_bytes) || !mask || ident < 0 || ident > m_pad ||
+      ident >= n)
+    return hipErrorInvalidValue;
+  if (ncols == 0) return hipSuccess;
+  const int bshift = log2_exact(block_bytes);
+  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
+  hipError_t e = hipMemsetAsync(mask, 0, size_t(batch) * size_t(nmask) * sizeof(int32_t), stream);
+  const DescView d0 = view(desc, n, m_pad, batch);
+  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
+    DescView d = d0;
+    d.in += size_t(b0) * size_t(n);
+    e = syndrome_launch<true>(d, n, m_pad, ident, unsigned(std::min(batch - b0, kMaxGridY)), ncols, force_bytewise,
+                              bshift, mask + size_t(b0) * size_t(nmask), stream);
+  }
+  return e;
 }
 
 hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
                             const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
                             hipStream_t stream) {
-  if (p < 1 || p > 16 || p >= n || !scrub_args_ok(n, pad_m(p), ncols, block_bytes) || !mask || !loc || !counts)
-    return hipErrorInvalidValue;
+  if (!locate_args_ok(n, p, ncols, block_bytes) || !mask || !loc || !counts) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(counts, 0, size_t(n + 2) * sizeof(uint64_t), stream);
   if (e != hipSuccess || ncols == 0) return e;
+  return locate_launch<false>(view(desc, n, pad_m(p)), n, p, 1, ncols, force_bytewise, log2_exact(block_bytes), mask,
+                              loc, locatable, counts, stream);
+}
+
+hipError_t launch_gf_locate_batched(const void* desc, int n, int p, int batch, int64_t ncols, bool force_bytewise,
+                                    int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
+                                    uint64_t* counts, hipStream_t stream) {
+  if (batch < 1 || !desc || !locate_args_ok(n, p, ncols, block_bytes) || !mask || !loc || !counts)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(counts, 0, size_t(batch) * size_t(n + 2) * sizeof(uint64_t), stream);
+  if (ncols == 0) return e;
   const int bshift = log2_exact(block_bytes);
-  const int span_shift = std::min(bshift, kLocSpanShift);
-  const int64_t nwg = (ncols + (int64_t(1) << span_shift) - 1) >> span_shift;
-  if (nwg > int64_t(INT32_MAX)) return hipErrorInvalidValue;
-  const DescView d = view(desc, n, pad_m(p));
-  return dispatch_tile(pad_m(p), [&](auto mt) -> hipError_t {
-    constexpr int MT = decltype(mt)::value;
-    gf_locate_kernel<MT><<<unsigned(nwg), kBlock, 0, stream>>>(d, n, p, ncols, bshift, span_shift, mask, loc,
-                                                               locatable ? 1 : 0, force_bytewise ? 1 : 0,
-                                                               reinterpret_cast<unsigned long long*>(counts));
-    return hipGetLastError();
-  });
+  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
+  const DescView d0 = view(desc, n, pad_m(p), batch);
+  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
+    DescView d = d0;
+    d.in += size_t(b0) * size_t(n);
+    e = locate_launch<true>(d, n, p, unsigned(std::min(batch - b0, kMaxGridY)), ncols, force_bytewise, bshift,
+                            mask + size_t(b0) * size_t(nmask), loc, locatable, counts + size_t(b0) * size_t(n + 2),
+                            stream);
+  }
+  return e;
 }
 
 }  // namespace gfrs

@@ -23,8 +23,8 @@ from .._native import cpu, hip
 from ..ops.gemm import Gemm16Plan, GemmPlan, _null, _rows
 from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, decode_system_into_plan
 from ..ops.matrix import decode_matrix, encoding_matrix
-from ..ops.scrub import (MAX_LOCATE_P, ScrubPlan, ScrubReport, check_block_bytes, cpu_scrub, make_report,
-                         stripe_rows)
+from ..ops.scrub import (MAX_LOCATE_P, BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport, StripeBatch,
+                         check_block_bytes, cpu_scrub, make_batch_report, make_report, stripe_rows)
 from ..ops.update import UpdatePlan, _window, check_overlap, cpu_update
 
 PITCH = 256
@@ -629,6 +629,92 @@ class ReedSolomon:
                 f"suspects {report.suspects}: not repairable from p={self.p} parity chunks")
         self.reconstruct(stripe, erased=report.suspects)
         return self.scrub(stripe)
+
+    # ---- batched scrub (small objects: B stripes per launch) ---------------------------------------
+    def _scrub_batch_setup(self, stripes, parity, block_bytes: int, what: str):
+        if self.field != "gf256":
+            raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
+        batch = StripeBatch(stripes, self.n, parity, self.k)
+        block_bytes = check_block_bytes(block_bytes)
+        plan = None
+        if batch.device.type == "cuda" and self.p > 0 and batch.nstripes > 0 and batch.ncols > 0:
+            key = ("scrubb", block_bytes) + batch.key
+            plan = self._plans.get(key)
+            if plan is None:
+                plan = self._plans[key] = BatchScrubPlan(batch, self.H, block_bytes)
+        return batch, block_bytes, plan
+
+    def syndrome_mask_batch(self, stripes, parity=None, block_bytes: int = 65536,
+                            stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+        """:meth:`syndrome_mask` for B stripes of one shape in ONE launch (grid.y = stripe): an int32
+        ``[B, ceil(C / block_bytes)]`` tensor on the stripes' device, row b the mask of stripe b. No
+        host sync. ``stripes``: a ``[B, n, C]`` tensor (any batch and row strides), or a sequence of
+        B stripes, each an ``[n, C]`` tensor or a list of n rows, natives first; with ``parity``
+        (``[B, p, C]``, what :meth:`encode_batch` returns) ``stripes`` holds the natives ``[B, k, C]``.
+        All rows have one length C. Any p."""
+        batch, block_bytes, plan = self._scrub_batch_setup(stripes, parity, block_bytes, "syndrome_mask_batch")
+        if plan is not None:
+            return plan.syndrome_mask(stream)
+        nmask = -(-batch.ncols // block_bytes)
+        mask = torch.zeros((batch.nstripes, nmask), dtype=torch.int32, device=batch.device)
+        if batch.device.type != "cuda" and self.p > 0 and nmask:
+            h = self.H
+            for b in range(batch.nstripes):
+                mask[b] = cpu_scrub(h, batch.rows(b), batch.ncols, block_bytes, self._cpu_gemm, locate=False)[0]
+        return mask
+
+    def scrub_batch(self, stripes, parity=None, block_bytes: int = 65536,
+                    stream: torch.cuda.Stream | None = None) -> BatchScrubReport:
+        """:meth:`scrub` for B stripes of one shape (the forms of :meth:`syndrome_mask_batch`): on
+        the GPU one launch of each kernel and one sync for the whole batch. Returns a
+        :class:`~gpu_rscode_amd.ops.scrub.BatchScrubReport`, whose ``report[b]`` equals what
+        :meth:`scrub` returns for stripe b alone. p > 16 raises ``NotImplementedError``."""
+        batch, block_bytes, plan = self._scrub_batch_setup(stripes, parity, block_bytes, "scrub_batch")
+        if self.p > MAX_LOCATE_P:
+            raise NotImplementedError(f"scrub_batch locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
+                                      "syndrome_mask_batch works for any p")
+        if plan is not None:
+            return plan.scrub(stream)
+        nstripes, nmask = batch.nstripes, -(-batch.ncols // block_bytes)
+        mask = torch.zeros((nstripes, nmask), dtype=torch.int32, device=batch.device)
+        votes = np.zeros((nstripes, self.n), dtype=np.int64)
+        unlocated, bad = np.zeros(nstripes, dtype=np.int64), np.zeros(nstripes, dtype=np.int64)
+        if batch.device.type != "cuda" and self.p > 0 and nmask:
+            h = self.H
+            for b in range(nstripes):
+                mask[b], votes[b], unlocated[b], bad[b] = cpu_scrub(h, batch.rows(b), batch.ncols, block_bytes,
+                                                                    self._cpu_gemm)
+        return make_batch_report(votes, unlocated, bad, mask)
+
+    def heal_batch(self, stripes, parity=None, report: BatchScrubReport | None = None) -> BatchScrubReport:
+        """Repair the dirty stripes of a batch in place, each from its own redundancy. Scrubs if no
+        ``report`` is given. A dirty stripe that passes :meth:`heal`'s rule (no unlocated column, 1..p
+        suspects) is rewritten with ``reconstruct(stripe_b, erased=suspects_b)``, one call per such
+        stripe; one that fails it is left byte for byte as it was and listed in ``unhealed``. Nothing
+        is raised for it: one bad object does not stop the batch. If anything was rewritten the whole
+        batch is scrubbed once more and that second report is returned, else the first; either has
+        ``unhealed`` filled in."""
+        if self.field != "gf256":
+            raise NotImplementedError(f"heal_batch is implemented for field='gf256', not {self.field!r}")
+        if report is None:
+            report = self.scrub_batch(stripes, parity)
+        batch = StripeBatch(stripes, self.n, parity, self.k)
+        unhealed, rewritten = [], False
+        for b in report.dirty:
+            rep = report.report[b]
+            if rep.unlocated > 0 or not rep.suspects or len(rep.suspects) > self.p:
+                unhealed.append(b)
+                continue
+            try:
+                self.reconstruct(batch.rows(b), erased=rep.suspects)
+            except UnrecoverableError:  # (a singular decode system is found before anything is written)
+                unhealed.append(b)
+                continue
+            rewritten = True
+        if rewritten:
+            report = self.scrub_batch(stripes, parity)
+        report.unhealed = unhealed
+        return report
 
     # ---- partial-stripe writes ----------------------------------------------------------------
     def _update_rows(self, what: str, changed, parity, first, second):

@@ -3,7 +3,7 @@ from .gemm import Gemm16Plan, GemmPlan, build_desc, desc_layout, gf_gemm, pad_m,
 from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_into_plan, gf_invert, invert_into_plan
 from .matrix import decode_matrix, encoding_matrix, gen_matrix_device, generator
 from .random import fill_random_
-from .scrub import ScrubPlan, ScrubReport
+from .scrub import BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport
 from .update import UpdatePlan
 
 __all__ = [
@@ -11,6 +11,6 @@ __all__ = [
     "PatternDecoder", "gf_invert", "invert_into_plan", "decode_system_into_plan", "decode_system16_into_plan", "decode_matrix", "encoding_matrix",
     "gen_matrix_device", "generator",
     "fill_random_",
-    "ScrubPlan", "ScrubReport",
+    "BatchScrubPlan", "BatchScrubReport", "ScrubPlan", "ScrubReport",
     "UpdatePlan",
 ]

@@ -13,6 +13,19 @@ k=10, n=14, C = 107,374,183). After a warm-up of every call it alternates, round
 each timed with device events over ``--reps`` calls, and prints the median and the spread (min,
 max) over the rounds. Then ``scrub`` on the clean stripe and on the stripe with one whole chunk
 overwritten. Prints one JSON object (also written to ``--out``).
+
+``--batch B`` measures the batched scrub of small objects instead: B stripes of ``--cols`` bytes per
+chunk, natives and ``encode_batch``'s parity in two allocations. Round by round it alternates
+
+  * (a) one ``syndrome_mask_batch`` call                      (one memset and one launch for B stripes),
+  * (b) a loop of B ``syndrome_mask`` calls on the same stripes (the API there was before; plans
+    cached and warm),
+  * (c) ``encode_batch`` on the same natives                   (the same number of rows moved),
+
+each timed with device events over a window of ``--reps`` calls (a call of (b) is the whole loop, and
+its window holds ``--reps`` / 8 of them), and, for (a) and (b), by the host clock around the same
+window ended by a synchronise: launch gaps are what the batched call removes. Then ``scrub_batch``
+on the clean batch and with one chunk of one stripe overwritten.
 """
 from __future__ import annotations
 
@@ -21,6 +34,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -35,6 +49,7 @@ def parse_args(argv=None):
     ap.add_argument("--rounds", type=int, default=21, help="alternations of the timed calls")
     ap.add_argument("--reps", type=int, default=40, help="calls per timed window")
     ap.add_argument("--scrub-reps", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=0, help="B > 0: the batched scrub of B stripes of --cols bytes")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     return ap.parse_args(argv)
 
@@ -42,6 +57,106 @@ def parse_args(argv=None):
 def spread(ms: list[float]) -> dict:
     return {"median_us": round(statistics.median(ms) * 1e3, 2), "min_us": round(min(ms) * 1e3, 2),
             "max_us": round(max(ms) * 1e3, 2)}
+
+
+def emit(res: dict, out: str | None) -> None:
+    line = json.dumps(res)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
+def main_batch(args) -> int:
+    import torch
+
+    from gpu_rscode_amd import ReedSolomon
+    from gpu_rscode_amd.models.rs import row_pitch
+    from gpu_rscode_amd.ops import fill_random_
+
+    k, n, C, bb, B = args.k, args.n, args.cols, args.block_bytes, args.batch
+    p = n - k
+    rs = ReedSolomon(k, n, matrix=args.matrix)
+    pitch = row_pitch(C, "cuda")
+    base = torch.empty(B * k * pitch, dtype=torch.uint8, device="cuda")
+    fill_random_(base, seed=1)
+    data = base.as_strided((B, k, C), (k * pitch, pitch, 1))
+    parity = rs.encode_batch(data)
+    stripes = [[data[b, j] for j in range(k)] + [parity[b, i] for i in range(p)] for b in range(B)]
+
+    def loop():
+        for rows in stripes:
+            rs.syndrome_mask(rows, bb)
+
+    calls = {
+        "syndrome_mask_batch": (lambda: rs.syndrome_mask_batch(data, parity, bb), args.reps),
+        "syndrome_mask_loop": (loop, max(1, args.reps // 8)),
+        "encode_batch": (lambda: rs.encode_batch(data, parity), args.reps),
+    }
+
+    def window(fn, reps) -> tuple[float, float]:
+        """(device-event ms, host-clock ms to the end of a synchronise) per call"""
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        s.record()
+        for _ in range(reps):
+            fn()
+        t.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(t) / reps, (time.perf_counter() - w0) * 1e3 / reps
+
+    # the batch is consistent, by both checks, and both give the same masks
+    mask = rs.syndrome_mask_batch(data, parity, bb)
+    assert tuple(mask.shape) == (B, -(-C // bb)) and not bool(mask.any().item())
+    assert not any(bool(rs.syndrome_mask(rows, bb).any().item()) for rows in stripes)
+    for fn, _ in calls.values():  # warm-up: code objects, every plan, the allocator's blocks
+        window(fn, 2)
+    dev = {name: [] for name in calls}
+    wall = {name: [] for name in calls}
+    for _ in range(args.rounds):
+        for name, (fn, reps) in calls.items():
+            d, w = window(fn, reps)
+            dev[name].append(d)
+            wall[name].append(w)
+    res = {"shape": {"k": k, "n": n, "matrix": args.matrix, "cols": C, "block_bytes": bb, "batch": B},
+           "rounds": args.rounds, "reps": {name: reps for name, (_, reps) in calls.items()},
+           "device": torch.cuda.get_device_name(0)}
+    for name in calls:
+        res[name] = spread(dev[name])
+    for name in ("syndrome_mask_batch", "syndrome_mask_loop"):
+        res[name + "_wall"] = spread(wall[name])
+    med = {name: statistics.median(ms) for name, ms in dev.items()}
+    res["loop_over_batch"] = round(med["syndrome_mask_loop"] / med["syndrome_mask_batch"], 2)
+    res["loop_over_batch_wall"] = round(statistics.median(wall["syndrome_mask_loop"]) /
+                                        statistics.median(wall["syndrome_mask_batch"]), 2)
+    res["batch_median_below_loop_min"] = bool(med["syndrome_mask_batch"] < min(dev["syndrome_mask_loop"]))
+    res["batch_over_encode_batch"] = round(med["syndrome_mask_batch"] / med["encode_batch"], 3)
+    res["syndrome_mask_batch_TBps"] = round(B * n * C / (med["syndrome_mask_batch"] * 1e-3) / 1e12, 3)
+    res["encode_batch_TBps"] = round(B * n * C / (med["encode_batch"] * 1e-3) / 1e12, 3)
+
+    if p > 16:  # beyond the locate kernel: masks only
+        res["scrub_batch"] = "not available for p > 16"
+        emit(res, args.out)
+        return 0
+    # scrub_batch (both kernels and the one sync): clean, then one chunk of one stripe overwritten
+    rep = rs.scrub_batch(data, parity, bb)
+    assert rep.clean.all() and rep.dirty == []
+    res["scrub_batch_clean"] = spread([window(lambda: rs.scrub_batch(data, parity, bb), 1)[0]
+                                       for _ in range(args.scrub_reps)])
+    vb, vj = B // 2, min(3, k - 1)
+    saved = data[vb, vj].clone()
+    fill_random_(data[vb, vj][: C // 16 * 16], seed=99)
+    rep = rs.scrub_batch(data, parity, bb)
+    assert rep.dirty == [vb] and rep.report[vb].suspects == [vj] and rep.unlocated[vb] == 0
+    res["scrub_batch_one_bad_chunk"] = spread([window(lambda: rs.scrub_batch(data, parity, bb), 1)[0]
+                                               for _ in range(args.scrub_reps)])
+    res["scrub_batch_one_bad_chunk"]["bad_columns"] = int(rep.bad_columns[vb])
+    healed = rs.heal_batch(data, parity, rep)
+    assert healed.clean.all() and healed.unhealed == [] and torch.equal(data[vb, vj], saved)
+    emit(res, args.out)
+    return 0
 
 
 def main(argv=None) -> int:
@@ -54,6 +169,8 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         print("scrub_bench.py needs a GPU", file=sys.stderr)
         return 2
+    if args.batch > 0:
+        return main_batch(args)
     k, n, C, bb = args.k, args.n, args.cols, args.block_bytes
     p = n - k
     rs = ReedSolomon(k, n, matrix=args.matrix)
@@ -124,12 +241,7 @@ def main(argv=None) -> int:
     res["scrub_one_bad_chunk"]["bad_columns"] = rep.bad_columns
     healed = rs.heal(stripe, rep)
     assert healed.clean and rs.verify(data, parity)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
     return 0
 
 
