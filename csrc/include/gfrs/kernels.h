@@ -130,13 +130,17 @@ hipError_t launch_gf_invert(const uint8_t* a, uint8_t* a_inv, int n, int batch, 
 // launch; larger ones (e.g. k = 2000, e = 100, or any e > 256) by the blocked multi-workgroup solve
 // (panels of pivot columns, row pivoting, rank-P updates over the chip), which needs a device
 // `workspace` of decode_system16_workspace(n, k, e) bytes (-1: too large even for it: e past
-// ~19 K). force_blocked takes the blocked solve for any size (tests).
+// ~19 K). force_blocked takes the blocked solve for any size (tests). force_panel (tests) sets the
+// blocked solve's panel width: 0 keeps the widest that fits the LDS (32 until e is about 2,200);
+// 4, 8, 16 or 32 run that instantiation in the same workspace when it is no wider than the default.
+// Any other value, a wider one, or a nonzero one for a system the one-workgroup kernel takes, is
+// hipErrorInvalidValue with nothing launched.
 bool decode_system16_supported(int n, int k, int e);
 int64_t decode_system16_workspace(int n, int k, int e);
 hipError_t launch_gf_decode_system16(const uint16_t* g, int n, int k, const int* rows, int* erased, int e,
                                      uint16_t* dm, int* status, void* desc, int m_pad, hipStream_t stream,
                                      const uint64_t* ptrs = nullptr, void* workspace = nullptr,
-                                     bool force_blocked = false);
+                                     bool force_blocked = false, int force_panel = 0);
 
 // ---- matrix utilities (csrc/kernels/gf_matrix.hip) -------------------------------------------
 // kind: 0 = reference Vandermonde, 1 = Cauchy. Writes the p x k block.

@@ -796,8 +796,10 @@ int64_t decode_system16_workspace(int n, int k, int e) {
 
 hipError_t launch_gf_decode_system16(const uint16_t* g, int n, int k, const int* rows, int* erased, int e,
                                      uint16_t* dm, int* status, void* desc, int m_pad, hipStream_t stream,
-                                     const uint64_t* ptrs, void* workspace, bool force_blocked) {
+                                     const uint64_t* ptrs, void* workspace, bool force_blocked, int force_panel) {
   if (!erased || (desc && e > m_pad) || (ptrs && !desc)) return hipErrorInvalidValue;
+  if (force_panel != 0 && force_panel != 4 && force_panel != 8 && force_panel != 16 && force_panel != 32)
+    return hipErrorInvalidValue;
   uint32_t* tab = nullptr;
   uint64_t* dptr = nullptr;
   if (desc) {
@@ -807,13 +809,19 @@ hipError_t launch_gf_decode_system16(const uint16_t* g, int n, int k, const int*
   }
   if (force_blocked || !decode_system16_supported(n, k, e)) {  // the blocked multi-workgroup solve
     if (!workspace || !blocked16_fits(n, k, e)) return hipErrorInvalidValue;
-    switch (panel_of(e)) {
+    // force_panel (tests): a narrower instantiation than panel_of(e) picks. Every array of the
+    // workspace that depends on P (ainv P x P, the snapshot e x P, Y P x W) shrinks with it and the
+    // others do not change, so the workspace sized for panel_of(e) covers every narrower layout,
+    // and the panel kernel's LDS only shrinks. A wider panel than panel_of(e) fits neither.
+    if (force_panel > panel_of(e)) return hipErrorInvalidValue;
+    switch (force_panel ? force_panel : panel_of(e)) {
       case 32: return launch_blocked16<32>(g, n, k, rows, erased, e, dm, status, tab, m_pad, ptrs, dptr, workspace, stream);
       case 16: return launch_blocked16<16>(g, n, k, rows, erased, e, dm, status, tab, m_pad, ptrs, dptr, workspace, stream);
       case 8: return launch_blocked16<8>(g, n, k, rows, erased, e, dm, status, tab, m_pad, ptrs, dptr, workspace, stream);
       default: return launch_blocked16<4>(g, n, k, rows, erased, e, dm, status, tab, m_pad, ptrs, dptr, workspace, stream);
     }
   }
+  if (force_panel) return hipErrorInvalidValue;  // (a panel width names the blocked solve only)
   const size_t lds = lds16(n, k, e);
   if (lds > 65536) {
     const hipError_t err = ensure_lds_optin(reinterpret_cast<const void*>(&gf_decode_system16_kernel));

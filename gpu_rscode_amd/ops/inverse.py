@@ -127,14 +127,17 @@ def decode16_device_supported(n: int, k: int, e: int) -> bool:
 def decode_system16_into_plan(g: torch.Tensor, rows: torch.Tensor, erased: torch.Tensor, plan: Gemm16Plan, *,
                               status: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None,
                               ptrs: torch.Tensor | None = None, dm: torch.Tensor | None = None,
-                              force_blocked: bool = False) -> torch.Tensor:
+                              force_blocked: bool = False, force_panel: int = 0) -> torch.Tensor:
     """GF(2^16) form of :func:`decode_system_into_plan` (``csrc/kernels/gf_decode16.hip``): ``g`` is
     the (n, k) generator as a 16-bit device tensor; ``erased`` (device int32 [e]) is always written
     by the kernel (derived from ``rows``); ``dm`` (optional, int16 [e, k]) receives the decode rows.
     Writes the plan's four-record tables (and with ``ptrs`` its row pointers). Graph-capturable.
     Systems past one workgroup's LDS (e.g. k = 2000, e = 100; any e > 256) take the blocked
     multi-workgroup solve with a device workspace cached on the plan (``force_blocked``: for any
-    size, tests). Returns the device status word (0 ok, 1 singular, 2 invalid survivor list)."""
+    size, tests; ``force_panel``: 4, 8, 16 or 32 runs the blocked solve with that panel width instead
+    of the widest that fits, 0; any other value, a wider one, or a nonzero one for a system the
+    one-workgroup kernel takes raises ``RuntimeError`` before anything is launched).
+    Returns the device status word (0 ok, 1 singular, 2 invalid survivor list)."""
     n, k = g.shape
     e = erased.numel()
     if plan.k != k or plan.m != e or rows.numel() != k:
@@ -166,7 +169,7 @@ def decode_system16_into_plan(g: torch.Tensor, rows: torch.Tensor, erased: torch
     hip().decode_system16(g.data_ptr(), n, k, rows.data_ptr(), erased.data_ptr(), e,
                           0 if dm is None else dm.data_ptr(), status.data_ptr(), plan.desc.data_ptr(), plan.m_pad,
                           st.cuda_stream, 0 if ptrs is None else ptrs.data_ptr(), 0 if ws is None else ws.data_ptr(),
-                          force_blocked)
+                          force_blocked, force_panel)
     if ws is not None and not torch.cuda.is_current_stream_capturing():
         ws.record_stream(st)
     if plan.engine == "mfma":
