@@ -18,6 +18,15 @@
 // for d changed natives and p parity rows: in_ptr[t] = old_t (or delta_t in the delta form),
 // copy_ptr[t] = new_t (0 in the delta form; read, not written), out_ptr[i] = parity_i (read and
 // written in place; 0 = padding row, skipped), tab[t][i] = the map of E[i][changed[t]].
+//
+// The batched update (`batch` stripes per launch, each changing d natives of its own) has a record
+// of its own, update_batch_layout(k, d, m_pad, batch): the same header {k, d, m_pad, batch}, then
+//   in_ptr[batch * d]        stripe b's old_t (delta_t) at [b*d + t]
+//   copy_ptr[batch * d]      new_t (0 in the delta form; read, not written)
+//   out_ptr[batch * m_pad]   parity_i at [b*m_pad + i] (0 = padding row, skipped)
+//   ids[batch * d]           int32, ids[b*d + t] in [0, k): the native that row t of stripe b is
+//   align 32, tab[k][m_pad]  the maps of the WHOLE code, tab[j][i] = the map of E[i][j], shared by
+//                            every stripe; row t of stripe b uses tab[ids[b*d + t]][.]
 #pragma once
 
 #include <cstdint>
@@ -48,6 +57,22 @@ constexpr DescLayout desc_layout(int k, int m_pad, int batch = 1) {
   l.copy_off = l.in_off + 8 * size_t(k) * size_t(batch);
   l.out_off = l.copy_off + 8 * size_t(k) * size_t(batch);
   l.tab_off = align_up(l.out_off + 8 * size_t(m_pad) * size_t(batch), 32);
+  l.bytes = l.tab_off + sizeof(PermTable) * size_t(k) * size_t(m_pad);
+  return l;
+}
+
+// Batched in-place parity update (csrc/kernels/gf_update.hip): d changed rows per stripe, their
+// native ids per stripe, and one table block of all k natives (the header comment has the record).
+struct UpdateBatchLayout {
+  size_t in_off, copy_off, out_off, ids_off, tab_off, bytes;
+};
+constexpr UpdateBatchLayout update_batch_layout(int k, int d, int m_pad, int batch) {
+  UpdateBatchLayout l{};
+  l.in_off = sizeof(DescHeader);
+  l.copy_off = l.in_off + 8 * size_t(d) * size_t(batch);
+  l.out_off = l.copy_off + 8 * size_t(d) * size_t(batch);
+  l.ids_off = l.out_off + 8 * size_t(m_pad) * size_t(batch);
+  l.tab_off = align_up(l.ids_off + 4 * size_t(d) * size_t(batch), 32);
   l.bytes = l.tab_off + sizeof(PermTable) * size_t(k) * size_t(m_pad);
   return l;
 }

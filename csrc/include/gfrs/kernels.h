@@ -100,6 +100,20 @@ hipError_t launch_gf_locate_batched(const void* desc, int n, int p, int batch, i
 constexpr int kUpdateMaxD = 8;  // 32 VGPRs of deltas per lane
 hipError_t launch_gf_update(const void* desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs,
                             bool store_new, bool force_bytewise, hipStream_t stream);
+// `batch` stripes of one shape per launch (grid.y = stripe; more than 65,535 stripes run as several
+// launches), each changing d natives of its own, for the small overwrites of a store of small
+// objects. desc: an update_batch_layout(k, d, m_pad, batch) record (gfrs/desc.h): stripe b's rows at
+// in_ptr[b*d + t], copy_ptr[b*d + t] and out_ptr[b*m_pad + i] (0 = padding, skipped), its native
+// ids at ids[b*d + t], each in [0, k) and distinct within a stripe (the caller's duty: the kernel
+// forms table addresses from them unchecked), and ONE table block tab[j][i] = the map of E[i][j] for
+// all k natives, shared by the batch. Per stripe exactly launch_gf_update with the tables of
+// E[:, ids[b]]; col0, ncols and the form are shared. force_bytewise (any row of any stripe not
+// 16-byte aligned) or col0 % 16 != 0 puts the whole batch on the byte-per-lane form. No row written
+// by one stripe may overlap any other row of the batch. hipErrorInvalidValue, and nothing launched,
+// for a null desc, batch < 1, k outside [1, 256], and whatever launch_gf_update refuses; ncols == 0
+// succeeds without a launch.
+hipError_t launch_gf_update_batched(const void* desc, int k, int d, int m_pad, int batch, int64_t col0, int64_t ncols,
+                                    bool pairs, bool store_new, bool force_bytewise, hipStream_t stream);
 
 // ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip) ---------------------------------------
 // Inverts `batch` n x n matrices (row-major, contiguous) with row pivoting, one workgroup each,

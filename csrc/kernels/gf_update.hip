@@ -16,6 +16,15 @@
 // still reads it, whereas a lane that reads and then writes its own 16 bytes of old_t is safe.
 // d <= kUpdateMaxD per launch (32 VGPRs of deltas); callers split longer lists into passes, which
 // XOR accumulation makes independent. No LDS, no atomics.
+//
+// Batched form (template flag BATCH, grid.y = stripe), for the small overwrites of a store of small
+// objects, where one launch per stripe is launch-bound: `batch` stripes of one shape, each changing d
+// natives OF ITS OWN. The record is update_batch_layout(k, d, m_pad, batch) (gfrs/desc.h): stripe b
+// has in[b*d + t], copy[b*d + t], out[b*m_pad + i] and d int32 ids, ids[b*d + t] in [0, k); the
+// table block holds the maps of all k natives and is shared. A wave never spans two stripes, so the
+// ids are wave-uniform: they are read through the constant address space and moved into SGPRs at the
+// top of the kernel (sgpr_int), and row t's table address is tab + (id_t * m_pad + i) * kPermStride,
+// all scalar. Everything else is the single form, whose code the flag leaves as it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,8 +52,10 @@ __device__ __forceinline__ void stb(uint64_t base, int64_t off, uint8_t v) {
 // One byte column at row offset `off` (rows of any alignment): the ragged tail of the vector form
 // and every lane of the byte form. d is a run-time count here; the delta bytes sit in registers
 // through the unrolled, guarded loops.
-template <int FORM>
-__device__ __forceinline__ void update_byte(const DescView& dv, int d, int m_pad, int64_t off) {
+// BATCH: row[t] is the table row (native id) of changed row t; else the table row is t itself.
+template <int FORM, bool BATCH = false>
+__device__ __forceinline__ void update_byte(const DescView& dv, int d, int m_pad, int64_t off,
+                                            const int (&row)[kUpdateMaxD]) {
   uint32_t x[kUpdateMaxD], y[kUpdateMaxD];
 #pragma unroll
   for (int t = 0; t < kUpdateMaxD; ++t) {
@@ -76,7 +87,7 @@ __device__ __forceinline__ void update_byte(const DescView& dv, int d, int m_pad
         for (int i = 0; i < 4; ++i) {
           // a padding slot past m_pad applies row m_pad - 1's map to an accumulator nobody stores
           const int ii = std::min(i0 + i, m_pad - 1);
-          acc[i] = mac_map(acc[i], dv.tab + (size_t(t) * m_pad + ii) * kPermStride, s);
+          acc[i] = mac_map(acc[i], dv.tab + (size_t(BATCH ? row[t] : t) * m_pad + ii) * kPermStride, s);
         }
       }
     }
@@ -86,13 +97,34 @@ __device__ __forceinline__ void update_byte(const DescView& dv, int d, int m_pad
   }
 }
 
+// Stripe b = blockIdx.y of a batched launch: its own d row pointers of each kind, its own m_pad
+// output pointers and its own d ids (offsets formed in 64 bits), the ids moved into SGPRs. Called at
+// the top of a kernel, before any divergent branch.
+template <bool BATCH>
+__device__ __forceinline__ void stripe(DescView& dv, cptr<int32_t> ids, int d, int m_pad, int (&row)[kUpdateMaxD]) {
+  if constexpr (BATCH) {
+    const uint64_t b = blockIdx.y;
+    dv.in += b * uint64_t(d);
+    dv.copy += b * uint64_t(d);
+    dv.out += b * uint64_t(m_pad);
+    ids += b * uint64_t(d);
+#pragma unroll
+    for (int t = 0; t < kUpdateMaxD; ++t)
+      if (t < d) row[t] = sgpr_int(ids[t]);
+  }
+}
+
 // Vector form. D = changed rows (compile time: the deltas are a register array), SUB = parity rows
 // per sub-tile = min(4, m_pad), so every sub-tile row has a table column. Lanes [0, ngroups) own a
 // 16-byte group each, lanes [ngroups, ngroups + tail) one byte of the ragged tail; the grid strides
 // over the lanes when it was capped. `base` = col0, a multiple of 16 here.
-template <int D, int SUB, int FORM>
+// BATCH: `ids` are the batch's native ids and blockIdx.y the stripe (stripe()); else ids is null and
+// never read.
+template <int D, int SUB, int FORM, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_update_vec_kernel(DescView dv, int m_pad, int64_t base, int64_t ngroups,
-                                                               int tail, int64_t nblk) {
+                                                               int tail, int64_t nblk, cptr<int32_t> ids) {
+  int row[kUpdateMaxD] = {};
+  stripe<BATCH>(dv, ids, D, m_pad, row);
   for (int64_t cb = blockIdx.x; cb < nblk; cb += gridDim.x) {
     const int64_t g = cb * kBlock + threadIdx.x;
     if (g < ngroups) {
@@ -128,9 +160,10 @@ __global__ __launch_bounds__(kBlock) void gf_update_vec_kernel(DescView dv, int 
           // (as gf_scrub.hip's rows kernel: the table pointer re-issued per row pair, so a pair's
           // scalar table loads wait only for the pair before it and are not all hoisted)
           asm volatile("" : "+s"(tb));
-          const auto t0 = (cptr<uint32_t>)tb + (size_t(t) * m_pad + i0) * kPermStride;
+          const auto t0 = (cptr<uint32_t>)tb + (size_t(BATCH ? row[t] : t) * m_pad + i0) * kPermStride;
           if (t + 1 < D) {
-            const auto t1 = t0 + size_t(m_pad) * kPermStride;
+            const auto t1 = BATCH ? (cptr<uint32_t>)tb + (size_t(row[t + 1]) * m_pad + i0) * kPermStride
+                                  : t0 + size_t(m_pad) * kPermStride;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
               const Sel s0 = make_sel(x[t][w]);
@@ -154,18 +187,20 @@ __global__ __launch_bounds__(kBlock) void gf_update_vec_kernel(DescView dv, int 
           if (op[i]) st16<true>(row_vec_w(op[i], off), u32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]});
       }
     } else if (g - ngroups < tail) {
-      update_byte<FORM>(dv, D, m_pad, base + ngroups * 16 + (g - ngroups));
+      update_byte<FORM, BATCH>(dv, D, m_pad, base + ngroups * 16 + (g - ngroups), row);
     }
   }
 }
 
 // Byte form: one lane per byte column, rows of any alignment, any col0.
-template <int FORM>
+template <int FORM, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_update_byte_kernel(DescView dv, int d, int m_pad, int64_t base,
-                                                                int64_t ncols, int64_t nblk) {
+                                                                int64_t ncols, int64_t nblk, cptr<int32_t> ids) {
+  int row[kUpdateMaxD] = {};
+  stripe<BATCH>(dv, ids, d, m_pad, row);
   for (int64_t cb = blockIdx.x; cb < nblk; cb += gridDim.x) {
     const int64_t c = cb * kBlock + threadIdx.x;
-    if (c < ncols) update_byte<FORM>(dv, d, m_pad, base + c);
+    if (c < ncols) update_byte<FORM, BATCH>(dv, d, m_pad, base + c, row);
   }
 }
 
@@ -183,62 +218,103 @@ inline Grid make_grid(int64_t items) {
   return g;
 }
 
-template <int D, int SUB>
-void launch_vec(int form, const DescView& dv, int m_pad, int64_t col0, int64_t ngroups, int tail, const Grid& g,
-                hipStream_t stream) {
+// In all of these BATCH picks the batched instantiation, `batch` is grid.y (1 when !BATCH) and `ids` the
+// ids of the first stripe of the launch (null when !BATCH).
+template <int D, int SUB, bool BATCH>
+void launch_vec(int form, const DescView& dv, cptr<int32_t> ids, int m_pad, int64_t col0, int64_t ngroups, int tail,
+                const Grid& g, unsigned batch, hipStream_t stream) {
+  const dim3 grid(g.blocks, batch);
   if (form == kDelta)
-    gf_update_vec_kernel<D, SUB, kDelta><<<g.blocks, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk);
+    gf_update_vec_kernel<D, SUB, kDelta, BATCH>
+        <<<grid, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk, ids);
   else if (form == kPairs)
-    gf_update_vec_kernel<D, SUB, kPairs><<<g.blocks, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk);
+    gf_update_vec_kernel<D, SUB, kPairs, BATCH>
+        <<<grid, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk, ids);
   else
-    gf_update_vec_kernel<D, SUB, kWrite><<<g.blocks, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk);
+    gf_update_vec_kernel<D, SUB, kWrite, BATCH>
+        <<<grid, kBlock, 0, stream>>>(dv, m_pad, col0, ngroups, tail, g.nblk, ids);
 }
 
-template <int D>
-void launch_vec_d(int form, const DescView& dv, int m_pad, int64_t col0, int64_t ngroups, int tail, const Grid& g,
-                  hipStream_t stream) {
+template <int D, bool BATCH>
+void launch_vec_d(int form, const DescView& dv, cptr<int32_t> ids, int m_pad, int64_t col0, int64_t ngroups, int tail,
+                  const Grid& g, unsigned batch, hipStream_t stream) {
   if (m_pad == 1)
-    launch_vec<D, 1>(form, dv, m_pad, col0, ngroups, tail, g, stream);
+    launch_vec<D, 1, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream);
   else if (m_pad == 2)
-    launch_vec<D, 2>(form, dv, m_pad, col0, ngroups, tail, g, stream);
+    launch_vec<D, 2, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream);
   else
-    launch_vec<D, 4>(form, dv, m_pad, col0, ngroups, tail, g, stream);
+    launch_vec<D, 4, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream);
 }
 
-}  // namespace
-
-hipError_t launch_gf_update(const void* desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs,
-                            bool store_new, bool force_bytewise, hipStream_t stream) {
-  if (!desc || d < 1 || d > kUpdateMaxD || m_pad < 1 || m_pad > 256 || m_pad % tile_for(m_pad) != 0 || col0 < 0 ||
-      ncols < 0 || (store_new && !pairs))
-    return hipErrorInvalidValue;
-  if (ncols == 0) return hipSuccess;
-  const DescView dv = view(desc, d, m_pad);
-  const int form = store_new ? kWrite : (pairs ? kPairs : kDelta);
+// One launch over `batch` stripes (grid.y); `dv` and `ids` are those of the first of them.
+template <bool BATCH>
+hipError_t update_launch(const DescView& dv, cptr<int32_t> ids, int d, int m_pad, unsigned batch, int64_t col0,
+                         int64_t ncols, int form, bool force_bytewise, hipStream_t stream) {
   if (force_bytewise || col0 % 16 != 0) {
     const Grid g = make_grid(ncols);
+    const dim3 grid(g.blocks, batch);
     if (form == kDelta)
-      gf_update_byte_kernel<kDelta><<<g.blocks, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk);
+      gf_update_byte_kernel<kDelta, BATCH><<<grid, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk, ids);
     else if (form == kPairs)
-      gf_update_byte_kernel<kPairs><<<g.blocks, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk);
+      gf_update_byte_kernel<kPairs, BATCH><<<grid, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk, ids);
     else
-      gf_update_byte_kernel<kWrite><<<g.blocks, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk);
+      gf_update_byte_kernel<kWrite, BATCH><<<grid, kBlock, 0, stream>>>(dv, d, m_pad, col0, ncols, g.nblk, ids);
     return hipGetLastError();
   }
   const int64_t ngroups = ncols / 16;
   const int tail = int(ncols % 16);
   const Grid g = make_grid(ngroups + tail);  // one extra lane per ragged tail byte
   switch (d) {
-    case 1: launch_vec_d<1>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 2: launch_vec_d<2>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 3: launch_vec_d<3>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 4: launch_vec_d<4>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 5: launch_vec_d<5>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 6: launch_vec_d<6>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    case 7: launch_vec_d<7>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
-    default: launch_vec_d<8>(form, dv, m_pad, col0, ngroups, tail, g, stream); break;
+    case 1: launch_vec_d<1, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 2: launch_vec_d<2, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 3: launch_vec_d<3, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 4: launch_vec_d<4, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 5: launch_vec_d<5, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 6: launch_vec_d<6, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    case 7: launch_vec_d<7, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
+    default: launch_vec_d<8, BATCH>(form, dv, ids, m_pad, col0, ngroups, tail, g, batch, stream); break;
   }
   return hipGetLastError();
+}
+
+bool update_args_ok(int d, int m_pad, int64_t col0, int64_t ncols, bool pairs, bool store_new) {
+  return d >= 1 && d <= kUpdateMaxD && m_pad >= 1 && m_pad <= 256 && m_pad % tile_for(m_pad) == 0 && col0 >= 0 &&
+         ncols >= 0 && (pairs || !store_new);
+}
+
+constexpr int kMaxGridY = 65535;  // stripes per launch, as launch_gf_syndrome_batched
+
+}  // namespace
+
+hipError_t launch_gf_update(const void* desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs,
+                            bool store_new, bool force_bytewise, hipStream_t stream) {
+  if (!desc || !update_args_ok(d, m_pad, col0, ncols, pairs, store_new)) return hipErrorInvalidValue;
+  if (ncols == 0) return hipSuccess;
+  const int form = store_new ? kWrite : (pairs ? kPairs : kDelta);
+  return update_launch<false>(view(desc, d, m_pad), nullptr, d, m_pad, 1, col0, ncols, form, force_bytewise, stream);
+}
+
+hipError_t launch_gf_update_batched(const void* desc, int k, int d, int m_pad, int batch, int64_t col0, int64_t ncols,
+                                    bool pairs, bool store_new, bool force_bytewise, hipStream_t stream) {
+  if (!desc || batch < 1 || k < 1 || k > 256 || !update_args_ok(d, m_pad, col0, ncols, pairs, store_new))
+    return hipErrorInvalidValue;
+  if (ncols == 0) return hipSuccess;
+  const int form = store_new ? kWrite : (pairs ? kPairs : kDelta);
+  const UpdateBatchLayout l = update_batch_layout(k, d, m_pad, batch);
+  const char* base = static_cast<const char*>(desc);
+  const DescView d0{(cptr<uint64_t>)(base + l.in_off), (cptr<uint64_t>)(base + l.copy_off),
+                    (cptr<uint64_t>)(base + l.out_off), (cptr<uint32_t>)(base + l.tab_off)};
+  const auto ids0 = (cptr<int32_t>)(base + l.ids_off);
+  hipError_t e = hipSuccess;
+  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
+    DescView dv = d0;
+    dv.in += size_t(b0) * size_t(d);
+    dv.copy += size_t(b0) * size_t(d);
+    dv.out += size_t(b0) * size_t(m_pad);
+    e = update_launch<true>(dv, ids0 + size_t(b0) * size_t(d), d, m_pad, unsigned(std::min(batch - b0, kMaxGridY)),
+                            col0, ncols, form, force_bytewise, stream);
+  }
+  return e;
 }
 
 }  // namespace gfrs

@@ -100,6 +100,17 @@ inline void bind_common(py::module_& m) {
     d["bytes"] = l.bytes;
     return d;
   }, py::arg("k"), py::arg("m_pad"), py::arg("batch") = 1);
+  m.def("update_batch_layout", [](int k, int d, int m_pad, int batch) {
+    const gfrs::UpdateBatchLayout l = gfrs::update_batch_layout(k, d, m_pad, batch);
+    py::dict r;
+    r["in_off"] = l.in_off;
+    r["copy_off"] = l.copy_off;
+    r["out_off"] = l.out_off;
+    r["ids_off"] = l.ids_off;
+    r["tab_off"] = l.tab_off;
+    r["bytes"] = l.bytes;
+    return r;
+  }, py::arg("k"), py::arg("d"), py::arg("m_pad"), py::arg("batch"));
   m.def("desc_layout16", [](int k, int m_pad, int batch) {
     const gfrs::DescLayout l = gfrs::desc_layout16(k, m_pad, batch);
     py::dict d;

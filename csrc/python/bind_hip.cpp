@@ -160,6 +160,16 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("d"), py::arg("m_pad"), py::arg("col0"), py::arg("ncols"), py::arg("pairs"),
       py::arg("store_new"), py::arg("bytewise"), py::arg("stream") = 0);
   m.def(
+      "update_batched",
+      [](uint64_t desc, int k, int d, int m_pad, int batch, int64_t col0, int64_t ncols, bool pairs, bool store_new,
+         bool bytewise, uint64_t stream) {
+        check(launch_gf_update_batched(reinterpret_cast<const void*>(desc), k, d, m_pad, batch, col0, ncols, pairs,
+                                       store_new, bytewise, as_stream(stream)),
+              "gf_update_batched");
+      },
+      py::arg("desc"), py::arg("k"), py::arg("d"), py::arg("m_pad"), py::arg("batch"), py::arg("col0"),
+      py::arg("ncols"), py::arg("pairs"), py::arg("store_new"), py::arg("bytewise"), py::arg("stream") = 0);
+  m.def(
       "invert",
       [](uint64_t a, uint64_t a_inv, int n, int batch, uint64_t status, uint64_t desc, uint64_t sel_rows, int mm,
          int m_pad, uint64_t stream) {

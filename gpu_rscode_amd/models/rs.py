@@ -25,7 +25,8 @@ from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, 
 from ..ops.matrix import decode_matrix, encoding_matrix
 from ..ops.scrub import (MAX_LOCATE_P, BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport, StripeBatch,
                          check_block_bytes, cpu_scrub, make_batch_report, make_report, stripe_rows)
-from ..ops.update import UpdatePlan, _window, check_overlap, cpu_update
+from ..ops.update import (BatchUpdatePlan, UpdatePlan, _PickPart, _window, batch_ids, batch_part, check_overlap,
+                          check_overlap_batch, check_parts, cpu_update)
 
 PITCH = 256
 
@@ -833,6 +834,120 @@ class ReedSolomon:
         ch, par, first, second, limit, dev = self._update_rows("write", changed, rows[self.k:], old, new)
         self._update("write", "write", ch, par, first, second, limit, dev, col0, ncols, stream, ident)
         return stripe
+
+    # ---- batched partial-stripe writes (small objects: B stripes per launch) -------------------------
+    def _update_batch(self, what, form, par, ids, first, second, col0, ncols, stream):
+        """The batched call behind update_batch / update_delta_batch / write_batch: ``par``, ``first``
+        and ``second`` are parts (ops.update.batch_part), ``ids`` the raw ``changed`` argument."""
+        nstripes = first.nstripes
+
+        def key(a):
+            return ("updb", form, par.key, first.key, None if second is None else second.key, a.shape, a.tobytes())
+        if first.device.type == "cuda" and isinstance(ids, np.ndarray):
+            # a repeat call on the same buffers and ids: dict lookups and the launches
+            plan = self._plans.get(key(ids))
+            if plan is not None:
+                plan.run(stream, col0, ncols)
+                return
+        ids = batch_ids(ids, nstripes, self.k, f"{what}: changed")
+        check_parts(par, first, second, self.p, ids.shape[1])
+        if nstripes == 0:
+            return
+        col0, ncols = _window(col0, ncols, first.ncols)
+        store_new = form == "write"
+        dev = first.device
+        fp = first.ptrs()
+        sp = None if second is None else second.ptrs()
+        check_overlap_batch(par.ptrs() if self.p else fp[:, :0], fp, sp, first.ncols, store_new)
+        if dev.type == "cuda" and self.wide:
+            raise NotImplementedError(f"{what} on the GPU is implemented for field='gf256' and 'gf16', "
+                                      f"not {self.field!r} (CPU tensors work)")
+        if self.wide and (col0 | ncols) & 1:
+            raise ValueError("GF(2^16) rows hold 16-bit symbols: col0 and ncols must be even byte counts")
+        if self.p == 0 or ncols == 0:
+            if store_new and ncols:  # nothing to update: a write only copies
+                with torch.cuda.stream(stream) if stream is not None and dev.type == "cuda" else _null():
+                    for b in range(nstripes):
+                        for a, c in zip(first.rows(b), second.rows(b)):
+                            a[col0: col0 + ncols].copy_(c[col0: col0 + ncols], non_blocking=True)
+            return
+        if dev.type == "cuda":
+            maps = self._maps(self.E)
+            plan = BatchUpdatePlan(par, first, second, changed=ids, coeff=None if maps is not None else self.E,
+                                   maps=maps, store_new=store_new, check=False)
+            self._plans[key(ids)] = plan
+            plan.run(stream, col0, ncols)
+            return
+        for b in range(nstripes):
+            cpu_update(self.E[:, ids[b]], par.rows(b), first.rows(b), None if second is None else second.rows(b),
+                       col0, ncols, self._cpu_gemm, store_new)
+
+    @staticmethod
+    def _batch_ids_fast(changed, nstripes):
+        """``changed`` as the int32 ``[B, d]`` array a plan is keyed on, unvalidated; or ``changed`` itself
+        when it is anything :func:`~gpu_rscode_amd.ops.update.batch_ids` has to look at first."""
+        if isinstance(changed, torch.Tensor):
+            if changed.device.type != "cpu" or changed.dtype not in (torch.int32, torch.int64):
+                return changed
+            a = changed.numpy()
+        else:
+            try:
+                a = np.asarray(changed)
+            except ValueError:
+                return changed
+        if a.dtype.kind not in "iu" or a.ndim not in (1, 2) or a.size == 0:
+            return changed
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (nstripes, a.shape[0]))
+        if a.size and (a.min() < -(1 << 31) or a.max() >= 1 << 31):
+            return changed
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def update_batch(self, parity, changed, old, new, col0: int = 0, ncols: int | None = None,
+                     stream: torch.cuda.Stream | None = None):
+        """:meth:`update` for B stripes of one shape in ONE launch (grid.y = stripe), each stripe with
+        changed natives of its own: small overwrites of small objects are launch-bound one by one.
+        ``parity``: ``[B, p, C]``, in place; ``old`` / ``new``: ``[B, d, C]``, only read. Each is a
+        tensor with any batch and row strides (last stride 1) or a sequence of B items, each a
+        ``[rows, C]`` tensor or a list of rows; all rows have one length C and the window ``[col0,
+        col0 + ncols)`` is shared by the batch. ``changed``: a sequence of d ids (every stripe changes
+        the same natives) or ``[B, d]`` ids as a nested list, an integer numpy array or a CPU integer
+        tensor (the ids are validated on the host: a CUDA tensor raises ``ValueError``); each row
+        holds 1..k distinct ids in ``[0, k)`` in any order, d the same for every stripe. Per stripe
+        the result is exactly that of :meth:`update`. No parity row may overlap any other row of any
+        stripe and no ``new`` row an ``old`` row (``ValueError``, nothing written). CPU tensors loop
+        over the stripes. Returns ``parity``."""
+        par = batch_part(parity, "parity")
+        self._update_batch("update_batch", "pair", par, self._batch_ids_fast(changed, par.nstripes),
+                           batch_part(old, "old"), batch_part(new, "new"), col0, ncols, stream)
+        return parity
+
+    def update_delta_batch(self, parity, changed, delta, col0: int = 0, ncols: int | None = None,
+                           stream: torch.cuda.Stream | None = None):
+        """:meth:`update_batch` from ``delta[b][t] = old ^ new`` (``[B, d, C]``), as :meth:`update_delta`.
+        Returns ``parity``."""
+        par = batch_part(parity, "parity")
+        self._update_batch("update_delta_batch", "delta", par, self._batch_ids_fast(changed, par.nstripes),
+                           batch_part(delta, "delta"), None, col0, ncols, stream)
+        return parity
+
+    def write_batch(self, stripes, changed, new, parity=None, col0: int = 0, ncols: int | None = None,
+                    stream: torch.cuda.Stream | None = None):
+        """:meth:`write` for B stripes of one shape in ONE launch: over the window natives
+        ``changed[b][t]`` of stripe b are overwritten with ``new[b][t]`` and its parity rows updated,
+        in one pass. ``stripes``: ``[B, n, C]`` (natives first), or the natives ``[B, k, C]`` with
+        ``parity`` ``[B, p, C]``, in the forms of :meth:`syndrome_mask_batch`; ``new``: ``[B, d, C]``
+        and ``changed`` as for :meth:`update_batch`. ``new`` must not overlap the rows that are
+        written. Returns ``stripes``."""
+        batch = StripeBatch(stripes, self.n, parity, self.k)
+        ids = self._batch_ids_fast(changed, batch.nstripes)
+        if not isinstance(ids, np.ndarray):
+            ids = batch_ids(ids, batch.nstripes, self.k, "write_batch: changed")
+        par = _PickPart(batch, np.broadcast_to(np.arange(self.k, self.n), (batch.nstripes, self.p)), tag="parity")
+        # (the old rows are picked by id: _update_batch validates the ids before any row is looked up)
+        self._update_batch("write_batch", "write", par, ids, _PickPart(batch, ids), batch_part(new, "new"), col0,
+                           ncols, stream)
+        return stripes
 
     def verify(self, data, parity) -> bool:
         """True when ``parity`` is the encoding of ``data`` (recomputes and compares)."""

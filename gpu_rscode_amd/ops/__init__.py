@@ -4,7 +4,7 @@ from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_in
 from .matrix import decode_matrix, encoding_matrix, gen_matrix_device, generator
 from .random import fill_random_
 from .scrub import BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport
-from .update import UpdatePlan
+from .update import BatchUpdatePlan, UpdatePlan
 
 __all__ = [
     "GemmPlan", "Gemm16Plan", "build_desc", "desc_layout", "gf_gemm", "pad_m", "tile_for", "perm_tables_from_coeff",
@@ -12,5 +12,5 @@ __all__ = [
     "gen_matrix_device", "generator",
     "fill_random_",
     "BatchScrubPlan", "BatchScrubReport", "ScrubPlan", "ScrubReport",
-    "UpdatePlan",
+    "BatchUpdatePlan", "UpdatePlan",
 ]

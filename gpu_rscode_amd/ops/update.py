@@ -5,7 +5,9 @@ Over GF(2^w) the parity of a stripe is linear in its natives, so when natives ``
 update needs the changed natives and the parity rows, not the other ``k - d`` natives, and the
 delta ``old ^ new`` is what a data node ships to a parity node. :class:`UpdatePlan` holds the
 device descriptors of that kernel (at most :data:`MAX_D` changed rows per launch, longer lists in
-passes); :func:`cpu_update` is the host form over the codec's C++ GEMM.
+passes); :func:`cpu_update` is the host form over the codec's C++ GEMM. :class:`BatchUpdatePlan` is
+the same for B stripes of one shape per launch (small objects), each stripe changing natives of its
+own: the kernel picks its coefficient maps by the ids it reads per stripe.
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ import torch
 
 from .._native import hip
 from .gemm import _check_rows, _rows, build_desc, pad_m, perm_tables_from_coeff, perm_tables_from_maps
+from .scrub import _ListPart, _TensorPart
 
 MAX_D = 8  # kUpdateMaxD: changed rows per launch (32 VGPRs of deltas per lane)
 _CPU_SCRATCH = 64 << 20  # bytes of scratch rows of the CPU form
@@ -147,3 +150,241 @@ def cpu_update(coeff: np.ndarray, parity, first, second, col0: int, ncols: int, 
     if store_new:
         for t in range(d):
             first[t][col0: col0 + ncols].copy_(second[t][col0: col0 + ncols])
+
+
+# ---- batched update: B stripes of one shape per launch, d changed natives of its own each --------
+def update_batch_layout(k: int, d: int, m_pad: int, batch: int) -> dict:
+    """Mirror of ``gfrs::update_batch_layout`` (``csrc/include/gfrs/desc.h``); a test pins the two equal."""
+    in_off = 16
+    copy_off = in_off + 8 * d * batch
+    out_off = copy_off + 8 * d * batch
+    ids_off = out_off + 8 * m_pad * batch
+    tab_off = (ids_off + 4 * d * batch + 31) // 32 * 32
+    return dict(in_off=in_off, copy_off=copy_off, out_off=out_off, ids_off=ids_off, tab_off=tab_off,
+                bytes=tab_off + 32 * k * m_pad)
+
+
+def build_update_batch_desc(ids: np.ndarray, first: np.ndarray, second: np.ndarray | None, parity: np.ndarray,
+                            tables: np.ndarray) -> np.ndarray:
+    """Descriptor bytes of one batched launch: ``ids`` int ``[B, d]``, ``first`` / ``second`` uint64 row
+    addresses ``[B, d]`` (``second`` None in the delta form), ``parity`` ``[B, p]``, ``tables`` the
+    (p, k, 8) uint32 v_perm records of the whole code."""
+    batch, d = ids.shape
+    p, k = tables.shape[:2]
+    mp = pad_m(p)
+    lay = update_batch_layout(k, d, mp, batch)
+    buf = np.zeros(lay["bytes"], dtype=np.uint8)
+
+    def put(off, a, dt):
+        raw = np.ascontiguousarray(a, dtype=dt).reshape(-1).view(np.uint8)
+        buf[off: off + raw.size] = raw
+
+    put(0, np.array([k, d, mp, batch]), "<i4")
+    put(lay["in_off"], first, "<u8")
+    if second is not None:
+        put(lay["copy_off"], second, "<u8")
+    out = np.zeros((batch, mp), dtype="<u8")
+    out[:, :p] = parity
+    put(lay["out_off"], out, "<u8")
+    put(lay["ids_off"], ids, "<i4")
+    t = np.zeros((k, mp, 8), dtype="<u4")
+    t[:, :p, :] = np.transpose(np.asarray(tables, dtype=np.uint32), (1, 0, 2))
+    put(lay["tab_off"], t, "<u4")
+    return buf
+
+
+def batch_ids(changed, nstripes: int, k: int, what: str = "changed") -> np.ndarray:
+    """The changed natives of a batch as a validated int32 ``[B, d]`` array. ``changed``: a sequence of
+    d ids (every stripe changes the same natives) or ``[B, d]`` ids as a nested list, an integer numpy
+    array or a CPU integer tensor; each row 1..k distinct ids in ``[0, k)``, any order. Ids are
+    validated on the host, so a CUDA tensor is refused. Anything else raises ``ValueError``."""
+    if isinstance(changed, torch.Tensor):
+        if changed.device.type != "cpu":
+            raise ValueError(f"{what}: ids are validated on the host and must be a CPU tensor, got {changed.device}")
+        if changed.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"{what}: ids must be integers, got {changed.dtype}")
+        a = changed.numpy()
+    else:
+        try:
+            a = np.asarray(changed)
+        except ValueError:  # a ragged nested list
+            raise ValueError(f"{what}: every stripe must list the same number of ids") from None
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"{what}: expected d ids or [B, d] ids (integers, one d for every stripe)")
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (nstripes, a.shape[0]))
+    if a.ndim != 2 or a.shape[0] != nstripes:
+        raise ValueError(f"{what}: expected d ids or [{nstripes}, d] ids, got shape {tuple(a.shape)}")
+    d = a.shape[1]
+    if not 1 <= d <= k:
+        raise ValueError(f"{what}: each stripe changes 1..k={k} natives, got {d}")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= k):
+        raise ValueError(f"{what}: ids must lie in [0, {k})")
+    srt = np.sort(a, axis=1)
+    dup = (srt[:, 1:] == srt[:, :-1]).any(axis=1)
+    if dup.any():
+        b = int(np.nonzero(dup)[0][0])
+        raise ValueError(f"{what}: stripe {b} lists a native twice: {a[b].tolist()}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class _PickPart:
+    """Rows ``idx[b, t]`` of stripe b of another part (or of a ``StripeBatch``): the changed natives
+    of a batched write, or its parity rows."""
+
+    def __init__(self, src, idx: np.ndarray, tag=None):
+        self.src, self.idx = src, np.ascontiguousarray(idx, dtype=np.int64)
+        self.nstripes, self.nrows = (int(v) for v in self.idx.shape)
+        self.ncols, self.device = src.ncols, src.device
+        self.key = ("p", src.key, tag if tag is not None else self.idx.tobytes())
+
+    def ptrs(self) -> np.ndarray:
+        return np.take_along_axis(self.src.ptrs(), self.idx, axis=1)
+
+    def rows(self, b: int) -> list[torch.Tensor]:
+        r = self.src.rows(b)
+        return [r[int(j)] for j in self.idx[b]]
+
+
+def batch_part(x, what: str):
+    """A row argument of a batched call as a part: a ``[B, rows, C]`` tensor, a sequence of B stripes
+    (each a ``[rows, C]`` tensor or a list of rows), or a part as it is."""
+    if isinstance(x, (_TensorPart, _ListPart, _PickPart)):
+        return x
+    return _TensorPart(x, what) if isinstance(x, torch.Tensor) else _ListPart(x, what)
+
+
+_KINDS = ("parity", "old", "new")
+
+
+def check_overlap_batch(parity: np.ndarray, first: np.ndarray, second: np.ndarray | None, ncols: int,
+                        first_written: bool = False) -> None:
+    """:func:`check_overlap` over a whole batch, on the uint64 ``[B, rows]`` address arrays of rows of
+    ``ncols`` bytes: ValueError when a parity row overlaps any other row of any stripe (so also for a
+    stripe listed twice), a ``second`` (new) row overlaps a ``first`` (old / delta) row, or, with
+    ``first_written``, two ``first`` rows overlap. The spans are sorted by start and each start
+    compared with the running maximum end; the kinds are looked at only if something overlaps."""
+    if ncols <= 0:
+        return
+    groups = [parity, first] + ([second] if second is not None else [])
+    start = np.concatenate([np.asarray(g).reshape(-1) for g in groups]).astype(np.int64)
+    if start.size < 2:
+        return
+    order = np.argsort(start, kind="stable")
+    s = start[order]
+    if not (s[1:] < s[:-1] + ncols).any():  # (equal lengths: the running maximum end is the previous end)
+        return
+    kind = np.concatenate([np.full(np.asarray(g).size, i, dtype=np.int8) for i, g in enumerate(groups)])[order]
+    before = np.concatenate([[False], s[1:] < s[:-1] + ncols])  # overlaps the span before it
+    after = np.concatenate([before[1:], [False]])               # ... the span after it
+
+    def reach(sel):  # does span i start inside a span of `sel` that starts no later (and comes before it)?
+        end = np.where(sel, s + ncols, np.iinfo(np.int64).min)
+        return s < np.concatenate([[np.iinfo(np.int64).min], np.maximum.accumulate(end)[:-1]])
+
+    bad = (kind == 0) & (before | after)
+    bad |= ((kind == 2) & reach(kind == 1)) | ((kind == 1) & reach(kind == 2))
+    if first_written:
+        bad |= (kind == 1) & reach(kind == 1)
+    if bad.any():
+        x = int(order[np.nonzero(bad)[0][0]])
+        for i, g in enumerate(groups):
+            g = np.asarray(g)
+            if x < g.size:
+                b, r = divmod(x, g.shape[1])
+                raise ValueError(f"{_KINDS[i]} row {r} of stripe {b} overlaps another row of the batch in memory: "
+                                 "the parity update works in place and needs disjoint rows")
+            x -= g.size
+
+
+class BatchUpdatePlan:
+    """A reusable device parity update of B stripes of one shape, one launch per pass (grid.y =
+    stripe), each stripe changing d natives of its own. As :class:`UpdatePlan` it keeps raw row
+    pointers only, so a cache may hand it out only for the caller's live tensors.
+
+    Args:
+        parity: ``[B, p, C]``: the parity rows, updated in place.
+        old_or_delta: ``[B, d, C]``: the natives' old contents (with ``new``) or the deltas.
+        new: ``[B, d, C]`` new contents, or None for the delta form.
+            Each of the three is a tensor (any batch and row strides, last stride 1) or a sequence of B
+            stripes, each a ``[rows, C]`` tensor or a list of rows; all rows on one GPU, of one length.
+        changed: d ids shared by every stripe, or ``[B, d]`` ids (:func:`batch_ids`).
+        coeff: the p x k encoding matrix of the WHOLE code over GF(2^8); or
+        maps: (p, k, 256) GF(2)-linear byte maps (the GF(16) nibble maps).
+        store_new: also overwrite ``old_or_delta`` with ``new`` in the same pass. Needs ``new``.
+        check: run the aliasing check (:func:`check_overlap_batch`); False when the caller has.
+    """
+
+    def __init__(self, parity, old_or_delta, new=None, *, changed, coeff=None, maps=None, store_new: bool = False,
+                 check: bool = True):
+        par, first = batch_part(parity, "parity"), batch_part(old_or_delta, "old" if new is not None else "delta")
+        second = None if new is None else batch_part(new, "new")
+        if store_new and second is None:
+            raise ValueError("store_new needs the new rows (the pair form)")
+        if coeff is not None:
+            tables = perm_tables_from_coeff(np.asarray(coeff, dtype=np.uint8))
+        elif maps is not None:
+            tables = perm_tables_from_maps(maps)
+        else:
+            raise ValueError("need coeff or maps")
+        self.p, self.k = (int(v) for v in tables.shape[:2])
+        self.batch = par.nstripes
+        if self.batch < 1 or not 1 <= self.p <= 255:
+            raise ValueError("BatchUpdatePlan needs at least one stripe and 1..255 parity rows")
+        ids = batch_ids(changed, self.batch, self.k)
+        self.d = ids.shape[1]
+        check_parts(par, first, second, self.p, self.d)
+        self.device = par.device
+        if self.device.type != "cuda":
+            raise ValueError("BatchUpdatePlan runs on a GPU")
+        self.pairs, self.store_new = second is not None, bool(store_new)
+        self.m_pad, self.ncols = pad_m(self.p), par.ncols
+        pp, fp = par.ptrs(), first.ptrs()
+        sp = None if second is None else second.ptrs()
+        if check:
+            check_overlap_batch(pp, fp, sp, self.ncols, self.store_new)
+        # one unaligned row: the whole batch bytewise
+        self.bytewise = any(bool((a % np.uint64(16)).any()) for a in (pp, fp, sp) if a is not None)
+        # one descriptor per pass of at most MAX_D changed rows of every stripe (ids[:, t0:t1])
+        self.passes = []
+        for t0 in range(0, self.d, MAX_D):
+            t1 = min(self.d, t0 + MAX_D)
+            host = build_update_batch_desc(ids[:, t0:t1], fp[:, t0:t1], None if sp is None else sp[:, t0:t1], pp,
+                                           tables)
+            self.passes.append((t1 - t0, torch.from_numpy(host).to(self.device)))
+        self._ready = torch.cuda.Event()
+        self._ready.record(torch.cuda.current_stream(self.device))
+
+    def run(self, stream: torch.cuda.Stream | None = None, col0: int = 0, ncols: int | None = None) -> None:
+        """Launch over byte columns ``[col0, col0 + ncols)`` of every stripe (default: to the end of
+        the rows) on ``stream`` (default: the current stream). No host sync."""
+        col0, ncols = _window(col0, ncols, self.ncols)
+        st = stream or torch.cuda.current_stream(self.device)
+        if self._ready is not None:
+            st.wait_event(self._ready)
+            self._ready = None
+        bytewise = self.bytewise or col0 % 16 != 0
+        for d, desc in self.passes:
+            if stream is not None:
+                desc.record_stream(stream)
+            hip().update_batched(int(desc.data_ptr()), self.k, d, self.m_pad, self.batch, col0, ncols, self.pairs,
+                                 self.store_new, bytewise, st.cuda_stream)
+
+
+def check_parts(par, first, second, p: int, d: int) -> None:
+    """ValueError unless the parts hold one number of stripes, p / d / d rows per stripe, one row
+    length and one device (a part without rows, the parity of a p = 0 code, has neither)."""
+    for part, want, name in ((par, p, "parity"), (first, d, "old / delta"), (second, d, "new")):
+        if part is None:
+            continue
+        if part.nstripes != first.nstripes:
+            raise ValueError(f"{first.nstripes} stripes of changed rows but {part.nstripes} of {name} rows")
+        if not part.nstripes:
+            continue
+        if part.nrows != want:
+            raise ValueError(f"expected {want} {name} rows per stripe, got {part.nrows}")
+        if part.nrows and part.ncols != first.ncols:
+            raise ValueError(f"rows must have one length ({first.ncols} vs {name} rows of {part.ncols})")
+        if part.nrows and part.device != first.device:
+            raise ValueError(f"all rows must live on one device ({first.device} vs {part.device})")

@@ -16,6 +16,11 @@ max) over the rounds, the achieved bytes/s over the rows each call moves, and th
 ``update`` no longer beats ``encode`` (``--sweep`` adds further d to find it). No time is fixed in
 advance: the comparison is ``encode`` on the same buffers in the same run. Prints one JSON object
 per code (also appended to ``--out``).
+
+``--batch`` times the batched small-object form instead: B stripes of ``--batch-codes`` (256 stripes of
+(10, 14) with 64 KiB and with 1 MiB chunks, and of (128, 160) with 64 KiB chunks), d = 1 with a random
+native per stripe, alternating ``update_batch`` (one launch), a loop of B cached ``update`` calls on
+the same buffers (B launches) and ``encode_batch`` on the same buffers.
 """
 from __future__ import annotations
 
@@ -28,6 +33,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 DEFAULT_CODES = "10:14:107374183,128:160:8388608"
+DEFAULT_BATCH_CODES = "10:14:65536:256,10:14:1048576:256,128:160:65536:256"
 
 
 def parse_args(argv=None):
@@ -37,6 +43,8 @@ def parse_args(argv=None):
     ap.add_argument("--rounds", type=int, default=15, help="alternations of the timed calls")
     ap.add_argument("--reps", type=int, default=20, help="calls per timed window")
     ap.add_argument("--sweep", default="8", help="further d for update, comma-separated (where k allows)")
+    ap.add_argument("--batch", action="store_true", help="time update_batch for the --batch-codes shapes instead")
+    ap.add_argument("--batch-codes", default=DEFAULT_BATCH_CODES, help="comma-separated k:n:bytes-per-chunk:stripes")
     ap.add_argument("--out", default=None, help="also append the JSON lines here")
     return ap.parse_args(argv)
 
@@ -123,6 +131,75 @@ def bench_code(torch, k: int, n: int, C: int, args) -> dict:
     return res
 
 
+def bench_batch(torch, k: int, n: int, C: int, B: int, args) -> dict:
+    """update_batch against a loop of B cached update calls and against encode_batch, d = 1."""
+    import numpy as np
+
+    from gpu_rscode_amd import ReedSolomon
+    from gpu_rscode_amd.models.rs import row_pitch
+    from gpu_rscode_amd.ops import fill_random_
+
+    p = n - k
+    rs = ReedSolomon(k, n, matrix=args.matrix)
+    pitch = row_pitch(C, "cuda")
+
+    def rows(r, seed):  # [B, r, C] over pitched storage, as encode_batch allocates its parity
+        base = torch.empty(B * r * pitch, dtype=torch.uint8, device="cuda")
+        fill_random_(base, seed=seed)
+        return base.as_strided((B, r, C), (r * pitch, pitch, 1))
+
+    data, parity, fresh, olds = rows(k, 1), rows(p, 2), rows(1, 3), rows(1, 4)
+    ids = np.random.default_rng(5).integers(0, k, size=(B, 1))
+    rs.encode_batch(data, parity)
+
+    # once, untimed: the batched update of every stripe's own native leaves a consistent stripe
+    for b in range(B):
+        olds[b, 0].copy_(data[b, int(ids[b, 0])])
+    rs.update_batch(parity, ids, olds, fresh)
+    for b in range(B):
+        data[b, int(ids[b, 0])].copy_(fresh[b, 0])
+    assert not bool(rs.syndrome_mask_batch(data, parity).any()), "update_batch differs from a re-encode"
+
+    def window(fn, reps) -> float:
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            fn()
+        t.record()
+        t.synchronize()
+        return s.elapsed_time(t) / reps
+
+    # the loop's arguments made once: a repeated update call is dict lookups and one launch
+    single = [(parity[b], [int(ids[b, 0])], olds[b], fresh[b]) for b in range(B)]
+
+    def loop():
+        for par, ch, old, new in single:
+            rs.update(par, ch, old, new)
+
+    calls = {"update_batch": lambda: rs.update_batch(parity, ids, olds, fresh), "update_loop": loop,
+             "encode_batch": lambda: rs.encode_batch(data, parity)}
+    for fn in calls.values():  # warm-up: code objects, plans, the allocator's blocks
+        window(fn, 3)
+    times = {name: [] for name in calls}
+    for _ in range(args.rounds):
+        for name, fn in calls.items():
+            times[name].append(window(fn, args.reps))
+    med = {name: statistics.median(ms) for name, ms in times.items()}
+    moved = {"update_batch": 2 + 2 * p, "update_loop": 2 + 2 * p, "encode_batch": k + p}
+    res = {"shape": {"k": k, "n": n, "matrix": args.matrix, "cols": C, "stripes": B, "d": 1}, "rounds": args.rounds,
+           "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+    for name, ms in times.items():
+        res[name] = spread(ms)
+        res[name]["rows_moved_per_stripe"] = moved[name]
+        res[name]["TBps"] = round(moved[name] * C * B / (med[name] * 1e-3) / 1e12, 3)
+    res["loop_over_batch"] = round(med["update_loop"] / med["update_batch"], 2)
+    res["batch_over_encode_batch"] = round(med["update_batch"] / med["encode_batch"], 3)
+    res["bytes_predict_batch_over_encode_batch"] = round((2 + 2 * p) / (k + p), 3)
+    rs.encode_batch(data, parity)
+    assert not bool(rs.syndrome_mask_batch(data, parity).any())
+    return res
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -134,9 +211,12 @@ def main(argv=None) -> int:
     if base_tune:
         print(f"ignoring GFRS_TUNE={base_tune}", file=sys.stderr)
     lines = []
-    for spec in args.codes.split(","):
-        k, n, C = (int(v) for v in spec.split(":"))
-        line = json.dumps(bench_code(torch, k, n, C, args))
+    for spec in (args.batch_codes if args.batch else args.codes).split(","):
+        if args.batch:
+            line = json.dumps(bench_batch(torch, *(int(v) for v in spec.split(":")), args))
+        else:
+            k, n, C = (int(v) for v in spec.split(":"))
+            line = json.dumps(bench_code(torch, k, n, C, args))
         print(line, flush=True)
         lines.append(line)
         torch.cuda.empty_cache()
