@@ -20,13 +20,14 @@ import torch
 
 from .. import gf
 from .._native import cpu, hip
-from ..ops.gemm import Gemm16Plan, GemmPlan, _null, _rows
+from ..ops.gemm import Gemm16Plan, GemmPlan
 from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, decode_system_into_plan
 from ..ops.matrix import decode_matrix, encoding_matrix
-from ..ops.scrub import (MAX_LOCATE_P, BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport, StripeBatch,
-                         check_block_bytes, cpu_scrub, make_batch_report, make_report, stripe_rows)
-from ..ops.update import (BatchUpdatePlan, UpdatePlan, _PickPart, _window, batch_ids, batch_part, check_overlap,
-                          check_overlap_batch, check_parts, cpu_update)
+from ..ops.rows import PickPart, StripeBatch, as_rows, batch_part, check_parts, null, stripe_rows, window
+from ..ops.scrub import (MAX_LOCATE_P, BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport, check_block_bytes,
+                         cpu_scrub, make_batch_report)
+from ..ops.update import (BatchUpdatePlan, UpdatePlan, batch_ids, check_overlap, check_overlap_batch,
+                          cpu_update)
 
 PITCH = 256
 
@@ -291,13 +292,13 @@ class ReedSolomon:
             if plan is not None:
                 plan.run(stream)
                 return parity
-        ins = _rows(data)
+        ins = as_rows(data)
         if len(ins) != self.k:
             raise ValueError(f"expected {self.k} data rows, got {len(ins)}")
         ncols = min(r.numel() for r in ins)
         if parity is None:
             parity = alloc_rows(self.p, ncols, ins[0].device)
-        outs = _rows(parity)
+        outs = as_rows(parity)
         if self.p == 0:
             return parity
         if ins[0].device.type == "cuda":
@@ -364,7 +365,7 @@ class ReedSolomon:
                 return out
             dm = self.decode_matrix(rows)[erased]
             for b in range(B):
-                self._cpu_gemm(dm, _rows(survivors[b]), [out[b, i] for i in erased])
+                self._cpu_gemm(dm, as_rows(survivors[b]), [out[b, i] for i in erased])
             return out
         key = ("decb", tuple(rows), int(survivors.data_ptr()), tuple(survivors.stride()), tuple(survivors.shape),
                int(out.data_ptr()), tuple(out.stride()))
@@ -464,7 +465,7 @@ class ReedSolomon:
             if plan is not None:
                 plan.run(stream)
                 return out
-        ins = _rows(survivors)
+        ins = as_rows(survivors)
         rows = [int(r) for r in rows]
         if len(ins) != self.k or len(rows) != self.k:
             raise ValueError(f"need exactly k={self.k} survivors")
@@ -472,7 +473,7 @@ class ReedSolomon:
         dev = ins[0].device
         if out is None:
             out = alloc_rows(self.k, ncols, dev)
-        outs = _rows(out)
+        outs = as_rows(out)
         pos = {r: j for j, r in enumerate(rows)}
         erased = [i for i in range(self.k) if i not in pos]
         copies = [outs[r] if r < self.k else None for r in rows]
@@ -531,7 +532,7 @@ class ReedSolomon:
                     stream: torch.cuda.Stream | None = None):
         """In-place repair of an n-row stripe: rewrite rows ``erased`` (natives and/or parity) from k
         surviving rows. One GEMM: rows = G[erased] . inv(G[survivors]) . survivors."""
-        rows_all = _rows(stripe)
+        rows_all = as_rows(stripe)
         if len(rows_all) != self.n:
             raise ValueError(f"stripe must have n={self.n} rows")
         erased = sorted(set(int(e) for e in erased))
@@ -558,18 +559,42 @@ class ReedSolomon:
         """The p x n parity-check matrix [E | I_p]: H . [data; parity] = 0 for a consistent stripe."""
         return gf.check_matrix(self.E)
 
-    def _scrub_setup(self, stripe, block_bytes: int, what: str):
+    def _scrub(self, what: str, batched: bool, stripes, parity, block_bytes: int, stream, locate: bool):
+        """The call behind :meth:`syndrome_mask` and :meth:`scrub` (``locate``) and their batched forms:
+        a cached plan on the GPU, else zeros (p = 0, nothing to check) or the CPU form stripe by stripe."""
         if self.field != "gf256":
             raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
-        rows, ncols, dev = stripe_rows(stripe, self.n)
+        if batched:
+            batch = StripeBatch(stripes, self.n, parity, self.k)
+            nstripes, ncols, dev = batch.nstripes, batch.ncols, batch.device
+        else:
+            rows, ncols, dev = stripe_rows(stripes, self.n)
+            nstripes = 1
         block_bytes = check_block_bytes(block_bytes)
-        plan = None
-        if dev.type == "cuda" and self.p > 0:
-            key = self._key(("scrub", block_bytes), rows)
+        # (a single stripe of no bytes still gets its plan, a batch of such stripes none: as ever)
+        if dev.type == "cuda" and self.p > 0 and nstripes > 0 and (ncols > 0 or not batched):
+            key = ("scrubb", block_bytes) + batch.key if batched else self._key(("scrub", block_bytes), rows)
             plan = self._plans.get(key)
             if plan is None:
-                plan = self._plans[key] = ScrubPlan(rows, self.H, block_bytes)
-        return rows, ncols, dev, block_bytes, plan
+                plan = BatchScrubPlan(batch, self.H, block_bytes) if batched else ScrubPlan(rows, self.H, block_bytes)
+                self._plans[key] = plan
+            return plan.scrub(stream) if locate else plan.syndrome_mask(stream)  # (scrub refuses p > 16 itself)
+        if locate and self.p > MAX_LOCATE_P:
+            raise NotImplementedError(f"{what} locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); syndrome_mask"
+                                      f"{'_batch' if batched else ''} works for any p")
+        nmask = -(-ncols // block_bytes)
+        mask = torch.zeros((nstripes, nmask), dtype=torch.int32, device=dev)
+        votes = np.zeros((nstripes, self.n), dtype=np.int64)
+        unlocated, bad = np.zeros(nstripes, dtype=np.int64), np.zeros(nstripes, dtype=np.int64)
+        if dev.type != "cuda" and self.p > 0 and nmask:
+            h = self.H
+            for b in range(nstripes):
+                mask[b], votes[b], unlocated[b], bad[b] = cpu_scrub(h, batch.rows(b) if batched else rows, ncols,
+                                                                    block_bytes, self._cpu_gemm, locate)
+        if not locate:
+            return mask if batched else mask[0]
+        report = make_batch_report(votes, unlocated, bad, mask)
+        return report if batched else report.report[0]
 
     def syndrome_mask(self, stripe, block_bytes: int = 65536, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         """Which column blocks of an n-row stripe (natives first, as for :meth:`reconstruct`) are
@@ -578,12 +603,7 @@ class ReedSolomon:
         for a consistent stripe. One fused pass that reads the n rows once and stores nothing but
         the mask; no host sync. Only columns ``[0, C)`` count (pitch padding is never read).
         ``block_bytes`` is a power of two >= 4096."""
-        rows, ncols, dev, block_bytes, plan = self._scrub_setup(stripe, block_bytes, "syndrome_mask")
-        if plan is not None:
-            return plan.syndrome_mask(stream)
-        if dev.type == "cuda":  # p = 0: nothing to check
-            return torch.zeros(-(-ncols // block_bytes), dtype=torch.int32, device=dev)
-        return cpu_scrub(self.H, rows, ncols, block_bytes, self._cpu_gemm, locate=False)[0]
+        return self._scrub("syndrome_mask", False, stripe, None, block_bytes, stream, False)
 
     def scrub(self, stripe, block_bytes: int = 65536, stream: torch.cuda.Stream | None = None) -> ScrubReport:
         """Check a stripe and name the chunks that are wrong: :meth:`syndrome_mask`, then every byte
@@ -596,17 +616,7 @@ class ReedSolomon:
         Location needs the columns of ``H`` to be pairwise independent and p >= 2 (checked when the
         plan is built); otherwise every bad column is unlocated and ``suspects`` is empty. Codes
         with p > 16 raise ``NotImplementedError`` (``syndrome_mask`` still works)."""
-        rows, ncols, dev, block_bytes, plan = self._scrub_setup(stripe, block_bytes, "scrub")
-        if self.p > MAX_LOCATE_P:
-            raise NotImplementedError(f"scrub locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
-                                      "syndrome_mask works for any p")
-        if plan is not None:
-            return plan.scrub(stream)
-        if dev.type == "cuda":
-            return make_report(np.zeros(self.n, dtype=np.int64), 0, 0,
-                               torch.zeros(-(-ncols // block_bytes), dtype=torch.int32, device=dev))
-        mask, votes, unlocated, bad = cpu_scrub(self.H, rows, ncols, block_bytes, self._cpu_gemm)
-        return make_report(votes, unlocated, bad, mask)
+        return self._scrub("scrub", False, stripe, None, block_bytes, stream, True)
 
     def heal(self, stripe, report: ScrubReport | None = None) -> ScrubReport:
         """Repair a stripe in place from its own redundancy. Scrubs if no ``report`` is given; a
@@ -632,19 +642,6 @@ class ReedSolomon:
         return self.scrub(stripe)
 
     # ---- batched scrub (small objects: B stripes per launch) ---------------------------------------
-    def _scrub_batch_setup(self, stripes, parity, block_bytes: int, what: str):
-        if self.field != "gf256":
-            raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
-        batch = StripeBatch(stripes, self.n, parity, self.k)
-        block_bytes = check_block_bytes(block_bytes)
-        plan = None
-        if batch.device.type == "cuda" and self.p > 0 and batch.nstripes > 0 and batch.ncols > 0:
-            key = ("scrubb", block_bytes) + batch.key
-            plan = self._plans.get(key)
-            if plan is None:
-                plan = self._plans[key] = BatchScrubPlan(batch, self.H, block_bytes)
-        return batch, block_bytes, plan
-
     def syndrome_mask_batch(self, stripes, parity=None, block_bytes: int = 65536,
                             stream: torch.cuda.Stream | None = None) -> torch.Tensor:
         """:meth:`syndrome_mask` for B stripes of one shape in ONE launch (grid.y = stripe): an int32
@@ -653,16 +650,7 @@ class ReedSolomon:
         B stripes, each an ``[n, C]`` tensor or a list of n rows, natives first; with ``parity``
         (``[B, p, C]``, what :meth:`encode_batch` returns) ``stripes`` holds the natives ``[B, k, C]``.
         All rows have one length C. Any p."""
-        batch, block_bytes, plan = self._scrub_batch_setup(stripes, parity, block_bytes, "syndrome_mask_batch")
-        if plan is not None:
-            return plan.syndrome_mask(stream)
-        nmask = -(-batch.ncols // block_bytes)
-        mask = torch.zeros((batch.nstripes, nmask), dtype=torch.int32, device=batch.device)
-        if batch.device.type != "cuda" and self.p > 0 and nmask:
-            h = self.H
-            for b in range(batch.nstripes):
-                mask[b] = cpu_scrub(h, batch.rows(b), batch.ncols, block_bytes, self._cpu_gemm, locate=False)[0]
-        return mask
+        return self._scrub("syndrome_mask_batch", True, stripes, parity, block_bytes, stream, False)
 
     def scrub_batch(self, stripes, parity=None, block_bytes: int = 65536,
                     stream: torch.cuda.Stream | None = None) -> BatchScrubReport:
@@ -670,22 +658,7 @@ class ReedSolomon:
         the GPU one launch of each kernel and one sync for the whole batch. Returns a
         :class:`~gpu_rscode_amd.ops.scrub.BatchScrubReport`, whose ``report[b]`` equals what
         :meth:`scrub` returns for stripe b alone. p > 16 raises ``NotImplementedError``."""
-        batch, block_bytes, plan = self._scrub_batch_setup(stripes, parity, block_bytes, "scrub_batch")
-        if self.p > MAX_LOCATE_P:
-            raise NotImplementedError(f"scrub_batch locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
-                                      "syndrome_mask_batch works for any p")
-        if plan is not None:
-            return plan.scrub(stream)
-        nstripes, nmask = batch.nstripes, -(-batch.ncols // block_bytes)
-        mask = torch.zeros((nstripes, nmask), dtype=torch.int32, device=batch.device)
-        votes = np.zeros((nstripes, self.n), dtype=np.int64)
-        unlocated, bad = np.zeros(nstripes, dtype=np.int64), np.zeros(nstripes, dtype=np.int64)
-        if batch.device.type != "cuda" and self.p > 0 and nmask:
-            h = self.H
-            for b in range(nstripes):
-                mask[b], votes[b], unlocated[b], bad[b] = cpu_scrub(h, batch.rows(b), batch.ncols, block_bytes,
-                                                                    self._cpu_gemm)
-        return make_batch_report(votes, unlocated, bad, mask)
+        return self._scrub("scrub_batch", True, stripes, parity, block_bytes, stream, True)
 
     def heal_batch(self, stripes, parity=None, report: BatchScrubReport | None = None) -> BatchScrubReport:
         """Repair the dirty stripes of a batch in place, each from its own redundancy. Scrubs if no
@@ -724,8 +697,8 @@ class ReedSolomon:
         if not 1 <= len(changed) <= self.k or len(set(changed)) != len(changed) or min(changed) < 0 \
                 or max(changed) >= self.k:
             raise ValueError(f"{what}: changed must be 1..k distinct native ids in [0, {self.k}), got {changed}")
-        par, first = _rows(parity), _rows(first)
-        second = None if second is None else _rows(second)
+        par, first = as_rows(parity), as_rows(first)
+        second = None if second is None else as_rows(second)
         if len(par) != self.p:
             raise ValueError(f"{what}: expected p={self.p} parity rows, got {len(par)}")
         if len(first) != len(changed) or (second is not None and len(second) != len(changed)):
@@ -762,7 +735,7 @@ class ReedSolomon:
         return None
 
     def _update(self, what, form, changed, par, first, second, limit, dev, col0, ncols, stream, ident=False):
-        col0, ncols = _window(col0, ncols, limit)
+        col0, ncols = window(col0, ncols, limit)
         store_new = form == "write"
         check_overlap(par, first, second, store_new)
         if dev.type == "cuda":
@@ -771,7 +744,7 @@ class ReedSolomon:
                                           f"not {self.field!r} (CPU tensors work)")
             if self.p == 0:
                 if store_new:
-                    with torch.cuda.stream(stream) if stream is not None else _null():
+                    with torch.cuda.stream(stream) if stream is not None else null():
                         for a, b in zip(first, second):
                             a[col0: col0 + ncols].copy_(b[col0: col0 + ncols], non_blocking=True)
                 return
@@ -827,7 +800,7 @@ class ReedSolomon:
         ident = self._update_again("write", changed, (stripe, new), col0, ncols, stream)
         if ident is None:
             return stripe
-        rows = _rows(stripe)
+        rows = as_rows(stripe)
         if len(rows) != self.n:
             raise ValueError(f"stripe must have n={self.n} rows")
         old = [rows[int(j)] for j in changed if 0 <= int(j) < self.k]
@@ -853,7 +826,7 @@ class ReedSolomon:
         check_parts(par, first, second, self.p, ids.shape[1])
         if nstripes == 0:
             return
-        col0, ncols = _window(col0, ncols, first.ncols)
+        col0, ncols = window(col0, ncols, first.ncols)
         store_new = form == "write"
         dev = first.device
         fp = first.ptrs()
@@ -866,7 +839,7 @@ class ReedSolomon:
             raise ValueError("GF(2^16) rows hold 16-bit symbols: col0 and ncols must be even byte counts")
         if self.p == 0 or ncols == 0:
             if store_new and ncols:  # nothing to update: a write only copies
-                with torch.cuda.stream(stream) if stream is not None and dev.type == "cuda" else _null():
+                with torch.cuda.stream(stream) if stream is not None and dev.type == "cuda" else null():
                     for b in range(nstripes):
                         for a, c in zip(first.rows(b), second.rows(b)):
                             a[col0: col0 + ncols].copy_(c[col0: col0 + ncols], non_blocking=True)
@@ -943,15 +916,15 @@ class ReedSolomon:
         ids = self._batch_ids_fast(changed, batch.nstripes)
         if not isinstance(ids, np.ndarray):
             ids = batch_ids(ids, batch.nstripes, self.k, "write_batch: changed")
-        par = _PickPart(batch, np.broadcast_to(np.arange(self.k, self.n), (batch.nstripes, self.p)), tag="parity")
+        par = PickPart(batch, np.broadcast_to(np.arange(self.k, self.n), (batch.nstripes, self.p)), tag="parity")
         # (the old rows are picked by id: _update_batch validates the ids before any row is looked up)
-        self._update_batch("write_batch", "write", par, ids, _PickPart(batch, ids), batch_part(new, "new"), col0,
+        self._update_batch("write_batch", "write", par, ids, PickPart(batch, ids), batch_part(new, "new"), col0,
                            ncols, stream)
         return stripes
 
     def verify(self, data, parity) -> bool:
         """True when ``parity`` is the encoding of ``data`` (recomputes and compares)."""
-        ins = _rows(data)
+        ins = as_rows(data)
         ref = self.encode(ins)
-        got = _rows(parity)
-        return all(torch.equal(a[: b.numel()], b[: a.numel()]) for a, b in zip(_rows(ref), got))
+        got = as_rows(parity)
+        return all(torch.equal(a[: b.numel()], b[: a.numel()]) for a, b in zip(as_rows(ref), got))

@@ -3,6 +3,7 @@ from .gemm import Gemm16Plan, GemmPlan, build_desc, desc_layout, gf_gemm, pad_m,
 from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_into_plan, gf_invert, invert_into_plan
 from .matrix import decode_matrix, encoding_matrix, gen_matrix_device, generator
 from .random import fill_random_
+from .rows import PickPart, StripeBatch, as_rows, batch_part, check_parts, stripe_part, stripe_rows
 from .scrub import BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport
 from .update import BatchUpdatePlan, UpdatePlan
 
@@ -13,4 +14,5 @@ __all__ = [
     "fill_random_",
     "BatchScrubPlan", "BatchScrubReport", "ScrubPlan", "ScrubReport",
     "BatchUpdatePlan", "UpdatePlan",
+    "PickPart", "StripeBatch", "as_rows", "batch_part", "check_parts", "stripe_part", "stripe_rows",
 ]

@@ -17,6 +17,7 @@ import torch
 from .. import gf
 from .._native import hip
 from ..utils.tune import tune_int, tune_str
+from .rows import as_rows, check_rows, null
 
 MAX_TILE = 16
 
@@ -112,33 +113,31 @@ def build_desc(in_ptrs: Sequence[int], out_ptrs: Sequence[int], copy_ptrs: Seque
 def _batched_rows(x) -> list[list[torch.Tensor]] | None:
     """[B, rows, C] tensor or list of per-stripe row lists -> list of stripes; None if not batched."""
     if isinstance(x, torch.Tensor):
-        return [_rows(x[b]) for b in range(x.shape[0])] if x.dim() == 3 else None
+        return [as_rows(x[b]) for b in range(x.shape[0])] if x.dim() == 3 else None
     if isinstance(x, (list, tuple)) and x and isinstance(x[0], (list, tuple)):
         return [list(s) for s in x]
     return None
 
 
-def _rows(x) -> list[torch.Tensor]:
-    if isinstance(x, torch.Tensor):
-        if x.dim() == 1:
-            return [x]
-        if x.dim() != 2:
-            raise ValueError("expected a 2-D [rows, bytes] tensor or a list of 1-D tensors")
-        return [x[i] for i in range(x.shape[0])]
-    return list(x)
+def ready_event(device: torch.device) -> torch.cuda.Event:
+    """An event after a new plan's descriptor uploads, which are ordered on the current stream."""
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    return ev
 
 
-def _check_rows(rows: list[torch.Tensor], what: str, device: torch.device | None) -> torch.device:
-    for r in rows:
-        if r.dtype != torch.uint8:
-            raise TypeError(f"{what} rows must be uint8, got {r.dtype}")
-        if r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
-            raise ValueError(f"{what} rows must be contiguous 1-D byte rows")
-        if device is None:
-            device = r.device
-        elif r.device != device:
-            raise ValueError(f"all rows must live on one device ({device} vs {r.device})")
-    return device
+def plan_stream(plan, stream: torch.cuda.Stream | None, *operands: torch.Tensor) -> torch.cuda.Stream:
+    """The stream a plan launches on (default: the current one). The plan's first launch waits there
+    for ``plan._ready`` (:func:`ready_event`); on a side stream the plan's device ``operands`` are
+    recorded as in use."""
+    st = stream or torch.cuda.current_stream(plan.device)
+    if plan._ready is not None:
+        st.wait_event(plan._ready)
+        plan._ready = None
+    if stream is not None:
+        for t in operands:
+            t.record_stream(stream)
+    return st
 
 
 class GemmPlan:
@@ -179,15 +178,15 @@ class GemmPlan:
                     raise ValueError("batched copies need one list of k destinations per stripe")
                 self._stripes_copy = [list(c) for c in copies]
                 copies = copies[0]
-        self.inputs = _rows(inputs)
-        self.outputs = _rows(outputs)
+        self.inputs = as_rows(inputs)
+        self.outputs = as_rows(outputs)
         self.copies = None if copies is None else [c for c in copies]
-        dev = _check_rows(self.inputs, "input", None)
-        dev = _check_rows(self.outputs, "output", dev)
+        dev = check_rows(self.inputs, "input", None)
+        dev = check_rows(self.outputs, "output", dev)
         if self.copies is not None:
             if len(self.copies) != len(self.inputs):
                 raise ValueError("copies must have one entry per input row")
-            dev = _check_rows([c for c in self.copies if c is not None], "copy", dev)
+            dev = check_rows([c for c in self.copies if c is not None], "copy", dev)
         if dev.type != "cuda":
             raise ValueError("GemmPlan runs on a GPU; use the CPU codec for host tensors")
         self.device = dev
@@ -196,14 +195,14 @@ class GemmPlan:
         all_in = [r for st in self._stripes_in for r in st] if self.batch > 1 else self.inputs
         all_out = [r for st in self._stripes_out for r in st] if self.batch > 1 else self.outputs
         if self.batch > 1:
-            _check_rows(all_in, "input", dev)
-            _check_rows(all_out, "output", dev)
+            check_rows(all_in, "input", dev)
+            check_rows(all_out, "output", dev)
             if any(len(st) != self.k for st in self._stripes_in) or any(len(st) != self.m for st in self._stripes_out):
                 raise ValueError("every stripe needs the same number of input / output rows")
         all_copy = ([c for st in self._stripes_copy for c in st] if self.batch > 1 and self.copies is not None
                     else (self.copies or []))
         if self.batch > 1 and self.copies is not None:
-            _check_rows([c for c in all_copy if c is not None], "copy", dev)
+            check_rows([c for c in all_copy if c is not None], "copy", dev)
         lens = [r.numel() for r in all_in + all_out + [c for c in all_copy if c is not None]]
         self.ncols = min(lens) if lens else 0
         if coeff is not None:
@@ -331,7 +330,7 @@ class GemmPlan:
         t = np.zeros((self.k, self.m_pad, 8), dtype="<u4")
         t[:, : self.m, :] = np.transpose(tables, (1, 0, 2))
         src = torch.from_numpy(np.frombuffer(t.tobytes(), dtype=np.uint8).copy())
-        with torch.cuda.stream(stream) if stream is not None else _null():
+        with torch.cuda.stream(stream) if stream is not None else null():
             self.desc[self.layout.tab_off :].copy_(src, non_blocking=False)
             if self.bitmat is not None:
                 self._build_bitmat(coeff)
@@ -529,20 +528,20 @@ class Gemm16Plan:
                 copies = stripes_copy[0]
             inputs, outputs = bi[0], bo[0]
         else:
-            bi, bo = [_rows(inputs)], [_rows(outputs)]
+            bi, bo = [as_rows(inputs)], [as_rows(outputs)]
             if copies is not None:
                 stripes_copy = [list(copies)]
-        self.inputs, self.outputs = _rows(inputs), _rows(outputs)
+        self.inputs, self.outputs = as_rows(inputs), as_rows(outputs)
         self.copies = None if copies is None else list(copies)
         if self.copies is not None and len(self.copies) != len(self.inputs):
             raise ValueError("copies must have one entry per input row")
         all_in = [r for st in bi for r in st]
         all_out = [r for st in bo for r in st]
         all_copy = [c for st in (stripes_copy or []) for c in st if c is not None]
-        dev = _check_rows(all_in, "input", None)
-        dev = _check_rows(all_out, "output", dev)
+        dev = check_rows(all_in, "input", None)
+        dev = check_rows(all_out, "output", dev)
         if all_copy:
-            dev = _check_rows(all_copy, "copy", dev)
+            dev = check_rows(all_copy, "copy", dev)
         if dev.type != "cuda":
             raise ValueError("Gemm16Plan runs on a GPU; use the CPU codec for host tensors")
         self.device = dev
@@ -672,17 +671,9 @@ class Gemm16Plan:
                      st.cuda_stream)
 
 
-class _null:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
-
-
 def gf_gemm(coeff, inputs, outputs=None, *, maps=None, copies=None, stream=None) -> torch.Tensor:
     """One-shot GF-GEMM. Returns the output tensor (allocated as [m, C] when ``outputs`` is None)."""
-    ins = _rows(inputs)
+    ins = as_rows(inputs)
     m = (np.asarray(coeff).shape[0] if coeff is not None else np.asarray(maps).shape[0])
     if outputs is None:
         c = min(r.numel() for r in ins)

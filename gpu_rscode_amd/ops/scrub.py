@@ -18,7 +18,8 @@ import torch
 
 from .. import gf
 from .._native import hip
-from .gemm import _check_rows, _rows, build_desc, pad_m, perm_tables_from_coeff
+from .gemm import build_desc, pad_m, perm_tables_from_coeff, plan_stream, ready_event
+from .rows import StripeBatch, stripe_part
 
 MIN_BLOCK_BYTES = 4096
 MAX_LOCATE_P = 16  # the locate kernel keeps one output tile of syndrome bytes per lane
@@ -65,96 +66,13 @@ def locate_table(h: np.ndarray) -> tuple[np.ndarray, bool]:
     return np.concatenate([h.reshape(-1), piv, pinv]), bool(p >= 2 and gf.columns_independent(h))
 
 
-def stripe_rows(stripe, n: int) -> tuple[list[torch.Tensor], int, torch.device]:
-    rows = _rows(stripe)
-    if len(rows) != n:
-        raise ValueError(f"stripe must have n={n} rows")
-    dev = _check_rows(rows, "stripe", None)
-    return rows, min(r.numel() for r in rows), dev
-
-
-class ScrubPlan:
-    """A reusable device scrub of one stripe's buffers, as ``GemmPlan(hold_buffers=False)``: it keeps
-    raw row pointers only, so a cache may hand it out only for the caller's live tensors.
-
-    Args:
-        rows: the n stripe rows (natives first) on one GPU.
-        h: the p x n check matrix over GF(2^8).
-        block_bytes: columns per mask word, a power of two >= 4096.
-    """
-
-    def __init__(self, rows, h: np.ndarray, block_bytes: int = 65536):
-        rows = _rows(rows)
-        h = np.asarray(h, dtype=np.uint8)
-        self.p, self.n = h.shape
-        if len(rows) != self.n:
-            raise ValueError(f"expected {self.n} stripe rows, got {len(rows)}")
-        self.device = _check_rows(rows, "stripe", None)
-        if self.device.type != "cuda":
-            raise ValueError("ScrubPlan runs on a GPU")
-        self.block_bytes = check_block_bytes(block_bytes)
-        self.ncols = min(r.numel() for r in rows)
-        self.nmask = -(-self.ncols // self.block_bytes)
-        self.m_pad = pad_m(self.p)
-        # H = [E | I_p]: the kernel may XOR the parity rows in as they are
-        systematic = self.p < self.n and np.array_equal(h[:, self.n - self.p:], np.eye(self.p, dtype=np.uint8))
-        self.ident = self.p if systematic else 0
-        ptrs = [int(r.data_ptr()) for r in rows]
-        self.bytewise = any(q % 16 for q in ptrs)
-        host = build_desc(ptrs, [0] * self.p, None, perm_tables_from_coeff(h))
-        self.desc = torch.from_numpy(host).to(self.device)
-        loc, self.locatable = locate_table(h)
-        self.loc = torch.from_numpy(loc).to(self.device) if self.p <= MAX_LOCATE_P else None
-        self._ready = torch.cuda.Event()
-        self._ready.record(torch.cuda.current_stream(self.device))
-
-    def _stream(self, stream: torch.cuda.Stream | None) -> torch.cuda.Stream:
-        st = stream or torch.cuda.current_stream(self.device)
-        if self._ready is not None:
-            st.wait_event(self._ready)
-            self._ready = None
-        if stream is not None:
-            self.desc.record_stream(stream)
-        return st
-
-    def syndrome_mask(self, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
-        """Launch the syndrome kernel; returns a fresh int32 ``[nmask]`` device tensor. No host sync."""
-        st = self._stream(stream)
-        with torch.cuda.stream(st):
-            mask = torch.empty(self.nmask, dtype=torch.int32, device=self.device)
-        if self.ncols:
-            hip().syndrome(int(self.desc.data_ptr()), self.n, self.m_pad, self.ident, self.ncols, self.bytewise,
-                           self.block_bytes, int(mask.data_ptr()), st.cuda_stream)
-        return mask
-
-    def scrub(self, stream: torch.cuda.Stream | None = None) -> ScrubReport:
-        """Both kernels back to back, then one sync (the copy of the counts to the host)."""
-        if self.p > MAX_LOCATE_P:
-            raise NotImplementedError(f"scrub locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
-                                      "syndrome_mask works for any p")
-        mask = self.syndrome_mask(stream)
-        st = stream or torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(st):
-            counts = torch.empty(self.n + 2, dtype=torch.int64, device=self.device)
-            if self.ncols:
-                if stream is not None:
-                    self.loc.record_stream(stream)
-                hip().locate(int(self.desc.data_ptr()), self.n, self.p, self.ncols, self.bytewise, self.block_bytes,
-                             int(mask.data_ptr()), int(self.loc.data_ptr()), self.locatable, int(counts.data_ptr()),
-                             st.cuda_stream)
-            else:
-                counts.zero_()
-            host = counts.cpu().numpy()
-        return make_report(host[: self.n].copy(), int(host[self.n]), int(host[self.n + 1]), mask)
-
-
 def make_report(votes: np.ndarray, unlocated: int, bad_columns: int, mask: torch.Tensor) -> ScrubReport:
-    votes = np.asarray(votes, dtype=np.int64)
-    return ScrubReport(bad_columns == 0, int(bad_columns), votes, int(unlocated),
+    votes, bad_columns = np.asarray(votes, dtype=np.int64), int(bad_columns)
+    return ScrubReport(bad_columns == 0, bad_columns, votes, int(unlocated),
                        [int(j) for j in np.nonzero(votes)[0]], mask)
 
 
-# ---- batched scrub: B stripes of one shape per launch ---------------------------------------------
+# ---- the report of B stripes scrubbed in one launch ------------------------------------------------
 class _StripeReports:
     """``BatchScrubReport.report``: ``report[b]`` is stripe b's :class:`ScrubReport`, made on demand."""
 
@@ -204,130 +122,27 @@ def make_batch_report(votes: np.ndarray, unlocated: np.ndarray, bad_columns: np.
                             np.asarray(votes, dtype=np.int64), mask, [int(b) for b in np.nonzero(bad_columns)[0]], [])
 
 
-class _TensorPart:
-    """Rows ``[:, j, :]`` of a ``[B, r, C]`` tensor (any batch and row strides, last stride 1)."""
+class _Scrub:
+    """What :class:`ScrubPlan` and :class:`BatchScrubPlan` share: everything but how they are built and
+    whether the launches and results carry a stripe axis (``_batched``)."""
 
-    def __init__(self, t: torch.Tensor, what: str):
-        if t.dim() != 3:
-            raise ValueError(f"{what}: expected a [B, rows, C] tensor or a sequence of stripes")
-        if t.dtype != torch.uint8:
-            raise ValueError(f"{what}: rows must be uint8, got {t.dtype}")
-        if t.shape[2] > 1 and t.stride(2) != 1:
-            raise ValueError(f"{what}: rows must be contiguous byte rows (last stride 1)")
-        self.t = t
-        self.nstripes, self.nrows, self.ncols = (int(v) for v in t.shape)
-        self.device = t.device
-        self.key = ("t", int(t.data_ptr()), tuple(t.shape), tuple(t.stride()))
-
-    def ptrs(self) -> np.ndarray:
-        t = self.t
-        b = np.arange(self.nstripes, dtype=np.int64)[:, None] * int(t.stride(0))
-        return (int(t.data_ptr()) + b + np.arange(self.nrows, dtype=np.int64)[None, :] * int(t.stride(1))).astype(np.uint64)
-
-    def rows(self, b: int) -> list[torch.Tensor]:
-        return [self.t[b, j] for j in range(self.nrows)]
-
-
-class _ListPart:
-    """A sequence of stripes, each an ``[r, C]`` tensor or a list of r rows."""
-
-    def __init__(self, stripes, what: str):
-        try:
-            self.stripes = [_rows(s) for s in stripes]
-        except TypeError:
-            raise ValueError(f"{what}: expected a [B, rows, C] tensor or a sequence of stripes") from None
-        self.nstripes = len(self.stripes)
-        self.nrows = len(self.stripes[0]) if self.stripes else 0
-        first = self.stripes[0][0] if self.nrows else None
-        if first is not None and not isinstance(first, torch.Tensor):
-            raise ValueError(f"{what}: rows must be uint8 tensors")
-        self.ncols = int(first.numel()) if first is not None else 0
-        self.device = first.device if first is not None else torch.device("cpu")
-        for rows in self.stripes:
-            if len(rows) != self.nrows:
-                raise ValueError(f"{what}: every stripe must have {self.nrows} rows, got {len(rows)}")
-            for r in rows:
-                if not isinstance(r, torch.Tensor) or r.dtype != torch.uint8:
-                    raise ValueError(f"{what}: rows must be uint8 tensors")
-                if r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
-                    raise ValueError(f"{what}: rows must be contiguous 1-D byte rows")
-                if r.numel() != self.ncols:
-                    raise ValueError(f"{what}: rows must have one length ({self.ncols} vs {r.numel()})")
-                if r.device != self.device:
-                    raise ValueError(f"{what}: all rows must live on one device ({self.device} vs {r.device})")
-        self._ptrs = np.array([[int(r.data_ptr()) for r in rows] for rows in self.stripes],
-                              dtype=np.uint64).reshape(self.nstripes, self.nrows)
-        self.key = ("l", self.ncols, self._ptrs.tobytes())
-
-    def ptrs(self) -> np.ndarray:
-        return self._ptrs
-
-    def rows(self, b: int) -> list[torch.Tensor]:
-        return self.stripes[b]
-
-
-class StripeBatch:
-    """B stripes of n byte rows of one length C on one device, in any of the forms the batched scrub
-    calls take: a ``[B, n, C]`` tensor; a sequence of B stripes, each an ``[n, C]`` tensor or a list of
-    n rows; or natives ``[B, k, C]`` with ``parity`` ``[B, p, C]`` in another allocation. ``key``
-    names the buffers (for a plan cache), ``ptrs()`` is the uint64 ``[B, n]`` row addresses,
-    ``rows(b)`` stripe b's row tensors. Anything else raises ``ValueError``."""
-
-    def __init__(self, stripes, n: int, parity=None, k: int | None = None):
-        parts = [("stripes", stripes)] if parity is None else [("stripes", stripes), ("parity", parity)]
-        self.parts = [_TensorPart(x, what) if isinstance(x, torch.Tensor) else _ListPart(x, what)
-                      for what, x in parts]
-        first = self.parts[0]
-        self.nstripes, self.ncols, self.device, self.n = first.nstripes, first.ncols, first.device, n
-        if parity is not None:
-            last = self.parts[1]
-            if last.nstripes != self.nstripes:
-                raise ValueError(f"{self.nstripes} stripes of natives but {last.nstripes} of parity")
-            if self.nstripes and (first.nrows, last.nrows) != (k, n - k):
-                raise ValueError(f"expected {k} native and {n - k} parity rows per stripe, "
-                                 f"got {first.nrows} and {last.nrows}")
-            if self.nstripes and last.ncols != self.ncols:
-                raise ValueError(f"native rows of {self.ncols} bytes but parity rows of {last.ncols}")
-            if self.nstripes and last.device != self.device:
-                raise ValueError(f"all rows must live on one device ({self.device} vs {last.device})")
-        elif self.nstripes and first.nrows != n:
-            raise ValueError(f"every stripe must have n={n} rows, got {first.nrows}")
-        self.key = tuple(part.key for part in self.parts)
-
-    def ptrs(self) -> np.ndarray:
-        return np.concatenate([part.ptrs() for part in self.parts], axis=1)
-
-    def rows(self, b: int) -> list[torch.Tensor]:
-        return [r for part in self.parts for r in part.rows(b)]
-
-
-class BatchScrubPlan:
-    """A reusable device scrub of B stripes of one shape, one launch per kernel (grid.y = stripe). As
-    :class:`ScrubPlan` it keeps raw row pointers only, so a cache may hand it out only for the
-    caller's live tensors.
-
-    Args:
-        stripes: B stripes of n rows each (natives first) as a list of row lists (or a
-            :class:`StripeBatch`), all rows on one GPU and of one length C.
-        h: the p x n check matrix over GF(2^8), shared by every stripe.
-        block_bytes: columns per mask word, a power of two >= 4096.
-    """
-
-    def __init__(self, stripes, h: np.ndarray, block_bytes: int = 65536):
-        h = np.asarray(h, dtype=np.uint8)
+    def _build(self, batch, nrows: int, h: np.ndarray, block_bytes: int) -> None:
+        """``batch``: a part or a ``StripeBatch`` of stripes of ``nrows`` rows."""
         self.p, self.n = h.shape
-        batch = stripes if isinstance(stripes, StripeBatch) else StripeBatch(stripes, self.n)
-        if batch.n != self.n:
-            raise ValueError(f"expected stripes of {self.n} rows, got {batch.n}")
+        if nrows != self.n:
+            raise ValueError(f"expected stripes of {self.n} rows, got {nrows}")
         if batch.nstripes < 1:
-            raise ValueError("BatchScrubPlan needs at least one stripe")
+            raise ValueError(f"{type(self).__name__} needs at least one stripe")
         self.device = batch.device
         if self.device.type != "cuda":
-            raise ValueError("BatchScrubPlan runs on a GPU")
+            raise ValueError(f"{type(self).__name__} runs on a GPU")
         self.block_bytes = check_block_bytes(block_bytes)
         self.batch, self.ncols = batch.nstripes, batch.ncols
+        self._lead = (self.batch,) if self._batched else ()  # the stripe axis of the launches and the results
         self.nmask = -(-self.ncols // self.block_bytes)
+        self._mask_shape = self._lead + (self.nmask,)
         self.m_pad = pad_m(self.p)
+        # H = [E | I_p]: the kernel may XOR the parity rows in as they are
         systematic = self.p < self.n and np.array_equal(h[:, self.n - self.p:], np.eye(self.p, dtype=np.uint8))
         self.ident = self.p if systematic else 0
         ptrs = batch.ptrs()
@@ -336,41 +151,80 @@ class BatchScrubPlan:
         self.desc = torch.from_numpy(host).to(self.device)
         loc, self.locatable = locate_table(h)
         self.loc = torch.from_numpy(loc).to(self.device) if self.p <= MAX_LOCATE_P else None
-        self._ready = torch.cuda.Event()
-        self._ready.record(torch.cuda.current_stream(self.device))
-
-    _stream = ScrubPlan._stream
+        self._ready = ready_event(self.device)
 
     def syndrome_mask(self, stream: torch.cuda.Stream | None = None) -> torch.Tensor:
-        """One launch for the whole batch; returns a fresh int32 ``[B, nmask]`` device tensor. No host
-        sync."""
-        st = self._stream(stream)
+        """Launch the syndrome kernel (one launch for a whole batch); returns a fresh int32 ``[nmask]``
+        (batched: ``[B, nmask]``) device tensor. No host sync."""
+        st = plan_stream(self, stream, self.desc)
         with torch.cuda.stream(st):
-            mask = torch.empty((self.batch, self.nmask), dtype=torch.int32, device=self.device)
+            mask = torch.empty(self._mask_shape, dtype=torch.int32, device=self.device)
         if self.ncols:
-            hip().syndrome_batched(int(self.desc.data_ptr()), self.n, self.m_pad, self.ident, self.batch, self.ncols,
-                                   self.bytewise, self.block_bytes, int(mask.data_ptr()), st.cuda_stream)
+            launch = hip().syndrome_batched if self._batched else hip().syndrome
+            launch(int(self.desc.data_ptr()), self.n, self.m_pad, self.ident, *self._lead, self.ncols, self.bytewise,
+                   self.block_bytes, int(mask.data_ptr()), st.cuda_stream)
         return mask
 
-    def scrub(self, stream: torch.cuda.Stream | None = None) -> BatchScrubReport:
-        """Both kernels back to back, then one sync (the copy of every stripe's counts to the host)."""
+    def scrub(self, stream: torch.cuda.Stream | None = None):
+        """Both kernels back to back, then one sync (the copy of the counts to the host). Returns a
+        :class:`ScrubReport` (batched: a :class:`BatchScrubReport`)."""
         if self.p > MAX_LOCATE_P:
             raise NotImplementedError(f"scrub locates chunks for p <= {MAX_LOCATE_P} (p = {self.p}); "
                                       "syndrome_mask works for any p")
         mask = self.syndrome_mask(stream)
         st = stream or torch.cuda.current_stream(self.device)
         with torch.cuda.stream(st):
-            counts = torch.empty((self.batch, self.n + 2), dtype=torch.int64, device=self.device)
+            counts = torch.empty(self._lead + (self.n + 2,), dtype=torch.int64, device=self.device)
             if self.ncols:
                 if stream is not None:
                     self.loc.record_stream(stream)
-                hip().locate_batched(int(self.desc.data_ptr()), self.n, self.p, self.batch, self.ncols, self.bytewise,
-                                     self.block_bytes, int(mask.data_ptr()), int(self.loc.data_ptr()), self.locatable,
-                                     int(counts.data_ptr()), st.cuda_stream)
+                launch = hip().locate_batched if self._batched else hip().locate
+                launch(int(self.desc.data_ptr()), self.n, self.p, *self._lead, self.ncols, self.bytewise,
+                       self.block_bytes, int(mask.data_ptr()), int(self.loc.data_ptr()), self.locatable,
+                       int(counts.data_ptr()), st.cuda_stream)
             else:
                 counts.zero_()
             host = counts.cpu().numpy()
-        return make_batch_report(host[:, : self.n].copy(), host[:, self.n].copy(), host[:, self.n + 1].copy(), mask)
+        report = make_batch_report if self._batched else make_report
+        return report(host[..., : self.n].copy(), host[..., self.n].copy(), host[..., self.n + 1].copy(), mask)
+
+
+class ScrubPlan(_Scrub):
+    """A reusable device scrub of one stripe's buffers, as ``GemmPlan(hold_buffers=False)``: it keeps
+    raw row pointers only, so a cache may hand it out only for the caller's live tensors.
+
+    Args:
+        rows: the n stripe rows (natives first) on one GPU; the shortest row bounds the columns.
+        h: the p x n check matrix over GF(2^8).
+        block_bytes: columns per mask word, a power of two >= 4096.
+    """
+
+    _batched = False
+
+    def __init__(self, rows, h: np.ndarray, block_bytes: int = 65536):
+        h = np.asarray(h, dtype=np.uint8)
+        part = stripe_part(rows, "stripe")
+        self._build(part, part.nrows, h, block_bytes)
+
+
+class BatchScrubPlan(_Scrub):
+    """A reusable device scrub of B stripes of one shape, one launch per kernel (grid.y = stripe). As
+    :class:`ScrubPlan` it keeps raw row pointers only, so a cache may hand it out only for the
+    caller's live tensors.
+
+    Args:
+        stripes: B stripes of n rows each (natives first) as a list of row lists (or a
+            :class:`~gpu_rscode_amd.ops.rows.StripeBatch`), all rows on one GPU and of one length C.
+        h: the p x n check matrix over GF(2^8), shared by every stripe.
+        block_bytes: columns per mask word, a power of two >= 4096.
+    """
+
+    _batched = True
+
+    def __init__(self, stripes, h: np.ndarray, block_bytes: int = 65536):
+        h = np.asarray(h, dtype=np.uint8)
+        batch = stripes if isinstance(stripes, StripeBatch) else StripeBatch(stripes, h.shape[1])
+        self._build(batch, batch.n, h, block_bytes)
 
 
 @lru_cache(maxsize=1)

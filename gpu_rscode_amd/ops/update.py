@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from .._native import hip
-from .gemm import _check_rows, _rows, build_desc, pad_m, perm_tables_from_coeff, perm_tables_from_maps
-from .scrub import _ListPart, _TensorPart
+from .gemm import build_desc, pad_m, perm_tables_from_coeff, perm_tables_from_maps, plan_stream, ready_event
+from .rows import as_rows, batch_part, check_parts, check_rows, window
 
 MAX_D = 8  # kUpdateMaxD: changed rows per launch (32 VGPRs of deltas per lane)
 _CPU_SCRATCH = 64 << 20  # bytes of scratch rows of the CPU form
@@ -26,7 +26,10 @@ def check_overlap(parity, first, second=None, first_written: bool = False) -> No
     """ValueError when, by address range, a parity row overlaps another parity row or any
     ``first`` (old / delta) or ``second`` (new) row, or a ``second`` row overlaps a ``first`` row; with
     ``first_written`` (a write stores into the old rows) also when two ``first`` rows overlap. The
-    kernel's read-modify-write is per lane and in place: it is wrong under such aliasing."""
+    kernel's read-modify-write is per lane and in place: it is wrong under such aliasing. This is
+    the rule of :func:`check_overlap_batch` for one stripe's lists of row tensors, each row of its own
+    length, kept as a loop over sorted spans: on the half dozen rows of a single update the array form
+    costs a fifth of the whole first call. ``tests/test_rows.py`` holds the two to one verdict."""
     spans = []
     for tag, rows in (("parity", parity), ("old", first), ("new", second or [])):
         for i, r in enumerate(rows):
@@ -44,15 +47,23 @@ def check_overlap(parity, first, second=None, first_written: bool = False) -> No
                                  "in place and needs disjoint rows")
 
 
-def _window(col0: int, ncols: int | None, limit: int) -> tuple[int, int]:
-    col0 = int(col0)
-    ncols = limit - col0 if ncols is None else int(ncols)
-    if col0 < 0 or ncols < 0 or col0 + ncols > limit:
-        raise ValueError(f"column range [{col0}, {col0 + ncols}) outside rows of {limit} bytes")
-    return col0, ncols
+class _Update:
+    """What :class:`UpdatePlan` and :class:`BatchUpdatePlan` share once built: ``passes``, a list of
+    ``(d, descriptor)``, and how they are launched. A subclass has ``_launch``."""
+
+    def run(self, stream: torch.cuda.Stream | None = None, col0: int = 0, ncols: int | None = None) -> None:
+        """Launch over byte columns ``[col0, col0 + ncols)`` of every stripe (default: to the end of
+        the shortest row) on ``stream`` (default: the current stream). No host sync."""
+        col0, ncols = window(col0, ncols, self.ncols)
+        st = plan_stream(self, stream)
+        bytewise = self.bytewise or col0 % 16 != 0
+        for d, desc in self.passes:
+            if stream is not None:
+                desc.record_stream(stream)
+            self._launch(int(desc.data_ptr()), d, col0, ncols, bytewise, st.cuda_stream)
 
 
-class UpdatePlan:
+class UpdatePlan(_Update):
     """A reusable device parity update, as ``ScrubPlan``: it keeps raw row pointers only, so a cache
     may hand it out only for the caller's live tensors.
 
@@ -67,8 +78,8 @@ class UpdatePlan:
     """
 
     def __init__(self, parity, old_or_delta, new=None, coeff=None, *, maps=None, store_new: bool = False):
-        par, first = _rows(parity), _rows(old_or_delta)
-        second = None if new is None else _rows(new)
+        par, first = as_rows(parity), as_rows(old_or_delta)
+        second = None if new is None else as_rows(new)
         if store_new and second is None:
             raise ValueError("store_new needs the new rows (the pair form)")
         self.p, self.d = len(par), len(first)
@@ -76,10 +87,10 @@ class UpdatePlan:
             raise ValueError("UpdatePlan needs 1..255 parity rows and at least one changed row")
         if second is not None and len(second) != self.d:
             raise ValueError(f"expected {self.d} new rows, got {len(second)}")
-        dev = _check_rows(par, "parity", None)
-        dev = _check_rows(first, "old" if second is not None else "delta", dev)
+        dev = check_rows(par, "parity", None)
+        dev = check_rows(first, "old" if second is not None else "delta", dev)
         if second is not None:
-            dev = _check_rows(second, "new", dev)
+            dev = check_rows(second, "new", dev)
         if dev.type != "cuda":
             raise ValueError("UpdatePlan runs on a GPU")
         self.device = dev
@@ -106,23 +117,10 @@ class UpdatePlan:
             host = build_desc([ptr(r) for r in first[t0:t1]], [ptr(r) for r in par],
                               None if second is None else [ptr(r) for r in second[t0:t1]], tables[:, t0:t1])
             self.passes.append((t1 - t0, torch.from_numpy(host).to(self.device)))
-        self._ready = torch.cuda.Event()
-        self._ready.record(torch.cuda.current_stream(self.device))
+        self._ready = ready_event(self.device)
 
-    def run(self, stream: torch.cuda.Stream | None = None, col0: int = 0, ncols: int | None = None) -> None:
-        """Launch over byte columns ``[col0, col0 + ncols)`` (default: to the end of the shortest row)
-        on ``stream`` (default: the current stream). No host sync."""
-        col0, ncols = _window(col0, ncols, self.ncols)
-        st = stream or torch.cuda.current_stream(self.device)
-        if self._ready is not None:
-            st.wait_event(self._ready)
-            self._ready = None
-        bytewise = self.bytewise or col0 % 16 != 0
-        for d, desc in self.passes:
-            if stream is not None:
-                desc.record_stream(stream)
-            hip().update(int(desc.data_ptr()), d, self.m_pad, col0, ncols, self.pairs, self.store_new, bytewise,
-                         st.cuda_stream)
+    def _launch(self, desc: int, d: int, col0: int, ncols: int, bytewise: bool, stream: int) -> None:
+        hip().update(desc, d, self.m_pad, col0, ncols, self.pairs, self.store_new, bytewise, stream)
 
 
 def cpu_update(coeff: np.ndarray, parity, first, second, col0: int, ncols: int, cpu_gemm, store_new: bool = False,
@@ -229,76 +227,54 @@ def batch_ids(changed, nstripes: int, k: int, what: str = "changed") -> np.ndarr
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-class _PickPart:
-    """Rows ``idx[b, t]`` of stripe b of another part (or of a ``StripeBatch``): the changed natives
-    of a batched write, or its parity rows."""
-
-    def __init__(self, src, idx: np.ndarray, tag=None):
-        self.src, self.idx = src, np.ascontiguousarray(idx, dtype=np.int64)
-        self.nstripes, self.nrows = (int(v) for v in self.idx.shape)
-        self.ncols, self.device = src.ncols, src.device
-        self.key = ("p", src.key, tag if tag is not None else self.idx.tobytes())
-
-    def ptrs(self) -> np.ndarray:
-        return np.take_along_axis(self.src.ptrs(), self.idx, axis=1)
-
-    def rows(self, b: int) -> list[torch.Tensor]:
-        r = self.src.rows(b)
-        return [r[int(j)] for j in self.idx[b]]
-
-
-def batch_part(x, what: str):
-    """A row argument of a batched call as a part: a ``[B, rows, C]`` tensor, a sequence of B stripes
-    (each a ``[rows, C]`` tensor or a list of rows), or a part as it is."""
-    if isinstance(x, (_TensorPart, _ListPart, _PickPart)):
-        return x
-    return _TensorPart(x, what) if isinstance(x, torch.Tensor) else _ListPart(x, what)
-
-
 _KINDS = ("parity", "old", "new")
 
 
-def check_overlap_batch(parity: np.ndarray, first: np.ndarray, second: np.ndarray | None, ncols: int,
+def check_overlap_batch(parity: np.ndarray, first: np.ndarray, second: np.ndarray | None, ncols,
                         first_written: bool = False) -> None:
-    """:func:`check_overlap` over a whole batch, on the uint64 ``[B, rows]`` address arrays of rows of
-    ``ncols`` bytes: ValueError when a parity row overlaps any other row of any stripe (so also for a
-    stripe listed twice), a ``second`` (new) row overlaps a ``first`` (old / delta) row, or, with
-    ``first_written``, two ``first`` rows overlap. The spans are sorted by start and each start
-    compared with the running maximum end; the kinds are looked at only if something overlaps."""
-    if ncols <= 0:
-        return
-    groups = [parity, first] + ([second] if second is not None else [])
-    start = np.concatenate([np.asarray(g).reshape(-1) for g in groups]).astype(np.int64)
-    if start.size < 2:
-        return
+    """The aliasing rule, on uint64 ``[B, rows]`` address arrays: ValueError when, by address range, a
+    parity row overlaps any other row of any stripe (so also for a stripe listed twice), a ``second``
+    (new) row overlaps a ``first`` (old / delta) row, or, with ``first_written`` (a write stores into
+    the old rows), two ``first`` rows overlap. The kernel's read-modify-write is per lane and in
+    place: it is wrong under such aliasing. ``ncols`` is the rows' one length, or a list with one
+    entry per address array given: that array's row length, or the array of its rows' lengths (the
+    form the single-stripe rule, :func:`check_overlap`, is tested against). Rows of no bytes overlap nothing. The
+    spans are sorted by start and each start compared with the running maximum end of the spans
+    before it; the kinds are looked at only if something overlaps."""
+    groups = [np.asarray(g) for g in (parity, first, second) if g is not None]
+    lens = list(ncols) if isinstance(ncols, (list, tuple)) else [ncols] * len(groups)
+    start = np.concatenate([g.reshape(-1) for g in groups]).astype(np.int64)
     order = np.argsort(start, kind="stable")
     s = start[order]
-    if not (s[1:] < s[:-1] + ncols).any():  # (equal lengths: the running maximum end is the previous end)
+    if all(np.ndim(n) == 0 for n in lens) and len(set(int(n) for n in lens)) == 1:
+        e = s + int(lens[0])
+    else:
+        e = s + np.concatenate([np.full(g.size, n) if np.ndim(n) == 0 else np.asarray(n).reshape(-1)
+                                for g, n in zip(groups, lens)])[order]
+    if not (s[1:] < np.maximum.accumulate(e)[:-1]).any():
         return
-    kind = np.concatenate([np.full(np.asarray(g).size, i, dtype=np.int8) for i, g in enumerate(groups)])[order]
-    before = np.concatenate([[False], s[1:] < s[:-1] + ncols])  # overlaps the span before it
-    after = np.concatenate([before[1:], [False]])               # ... the span after it
+    lowest = np.iinfo(np.int64).min
 
-    def reach(sel):  # does span i start inside a span of `sel` that starts no later (and comes before it)?
-        end = np.where(sel, s + ncols, np.iinfo(np.int64).min)
-        return s < np.concatenate([[np.iinfo(np.int64).min], np.maximum.accumulate(end)[:-1]])
+    def reach(sel):  # does span i, of some bytes, start inside a span of `sel` that comes before it in start order?
+        end = np.where(sel, e, lowest)
+        return (e > s) & (s < np.concatenate([[lowest], np.maximum.accumulate(end)[:-1]]))
 
-    bad = (kind == 0) & (before | after)
+    kind = np.concatenate([np.full(g.size, i, dtype=np.int8) for i, g in enumerate(groups)])[order]
+    bad = reach(kind == 0) | ((kind == 0) & reach(True))
     bad |= ((kind == 2) & reach(kind == 1)) | ((kind == 1) & reach(kind == 2))
     if first_written:
         bad |= (kind == 1) & reach(kind == 1)
     if bad.any():
         x = int(order[np.nonzero(bad)[0][0]])
         for i, g in enumerate(groups):
-            g = np.asarray(g)
             if x < g.size:
                 b, r = divmod(x, g.shape[1])
-                raise ValueError(f"{_KINDS[i]} row {r} of stripe {b} overlaps another row of the batch in memory: "
-                                 "the parity update works in place and needs disjoint rows")
+                raise ValueError(f"{_KINDS[i]} row {r} of stripe {b} overlaps another row in memory: the parity "
+                                 "update works in place and needs disjoint rows")
             x -= g.size
 
 
-class BatchUpdatePlan:
+class BatchUpdatePlan(_Update):
     """A reusable device parity update of B stripes of one shape, one launch per pass (grid.y =
     stripe), each stripe changing d natives of its own. As :class:`UpdatePlan` it keeps raw row
     pointers only, so a cache may hand it out only for the caller's live tensors.
@@ -353,38 +329,8 @@ class BatchUpdatePlan:
             host = build_update_batch_desc(ids[:, t0:t1], fp[:, t0:t1], None if sp is None else sp[:, t0:t1], pp,
                                            tables)
             self.passes.append((t1 - t0, torch.from_numpy(host).to(self.device)))
-        self._ready = torch.cuda.Event()
-        self._ready.record(torch.cuda.current_stream(self.device))
+        self._ready = ready_event(self.device)
 
-    def run(self, stream: torch.cuda.Stream | None = None, col0: int = 0, ncols: int | None = None) -> None:
-        """Launch over byte columns ``[col0, col0 + ncols)`` of every stripe (default: to the end of
-        the rows) on ``stream`` (default: the current stream). No host sync."""
-        col0, ncols = _window(col0, ncols, self.ncols)
-        st = stream or torch.cuda.current_stream(self.device)
-        if self._ready is not None:
-            st.wait_event(self._ready)
-            self._ready = None
-        bytewise = self.bytewise or col0 % 16 != 0
-        for d, desc in self.passes:
-            if stream is not None:
-                desc.record_stream(stream)
-            hip().update_batched(int(desc.data_ptr()), self.k, d, self.m_pad, self.batch, col0, ncols, self.pairs,
-                                 self.store_new, bytewise, st.cuda_stream)
-
-
-def check_parts(par, first, second, p: int, d: int) -> None:
-    """ValueError unless the parts hold one number of stripes, p / d / d rows per stripe, one row
-    length and one device (a part without rows, the parity of a p = 0 code, has neither)."""
-    for part, want, name in ((par, p, "parity"), (first, d, "old / delta"), (second, d, "new")):
-        if part is None:
-            continue
-        if part.nstripes != first.nstripes:
-            raise ValueError(f"{first.nstripes} stripes of changed rows but {part.nstripes} of {name} rows")
-        if not part.nstripes:
-            continue
-        if part.nrows != want:
-            raise ValueError(f"expected {want} {name} rows per stripe, got {part.nrows}")
-        if part.nrows and part.ncols != first.ncols:
-            raise ValueError(f"rows must have one length ({first.ncols} vs {name} rows of {part.ncols})")
-        if part.nrows and part.device != first.device:
-            raise ValueError(f"all rows must live on one device ({first.device} vs {part.device})")
+    def _launch(self, desc: int, d: int, col0: int, ncols: int, bytewise: bool, stream: int) -> None:
+        hip().update_batched(desc, self.k, d, self.m_pad, self.batch, col0, ncols, self.pairs, self.store_new,
+                             bytewise, stream)

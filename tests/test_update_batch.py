@@ -14,7 +14,8 @@ import test_update as cases
 from gpu_rscode_amd import ReedSolomon, gf
 from gpu_rscode_amd._native import cpu
 from gpu_rscode_amd.ops import BatchUpdatePlan
-from gpu_rscode_amd.ops.update import batch_ids, batch_part, check_overlap_batch, update_batch_layout
+from gpu_rscode_amd.ops.rows import batch_part
+from gpu_rscode_amd.ops.update import batch_ids, check_overlap_batch, update_batch_layout
 
 # p = 1 | SUB = 2 | the flagship | p = 5, a padded sub-tile | p = 17, m_pad = 32 | wide
 NARROW = [(3, 4, "vandermonde"), (4, 6, "cauchy"), (10, 14, "vandermonde"), (5, 10, "cauchy"), (19, 36, "cauchy")]
