@@ -77,6 +77,28 @@ constexpr UpdateBatchLayout update_batch_layout(int k, int d, int m_pad, int bat
   return l;
 }
 
+// Batched repair (csrc/kernels/gf_repair.hip): `batch` stripes per launch, each with an erasure
+// pattern of its own out of `npat` distinct ones, so the coefficient tables differ per stripe:
+//   header {k, m_pad, batch, npat}
+//   in_ptr [batch * k]       stripe b's k survivor rows, in the order of its pattern's coefficient columns
+//   out_ptr[batch * m_pad]   the rows stripe b rewrites (0 = padding / fewer erasures than m_pad: skipped)
+//   pat    [batch]           int32, pat[b] in [0, npat): the pattern of stripe b
+//   align 32, tab[npat][k][m_pad]   PermTable records, tab[q][j][i] = the map of coeff_q[i][j]; rows i >= e_q are zero
+// The host resolves survivor and erased chunk ids into row addresses: the kernel needs no chunk ids,
+// only pat[b], from which it forms its table block tab + pat[b] * k * m_pad records.
+struct RepairBatchLayout {
+  size_t in_off, out_off, pat_off, tab_off, bytes;
+};
+constexpr RepairBatchLayout repair_batch_layout(int k, int m_pad, int batch, int npat) {
+  RepairBatchLayout l{};
+  l.in_off = sizeof(DescHeader);
+  l.out_off = l.in_off + 8 * size_t(k) * size_t(batch);
+  l.pat_off = l.out_off + 8 * size_t(m_pad) * size_t(batch);
+  l.tab_off = align_up(l.pat_off + 4 * size_t(batch), 32);
+  l.bytes = l.tab_off + sizeof(PermTable) * size_t(npat) * size_t(k) * size_t(m_pad);
+  return l;
+}
+
 // GF(2^16) descriptor (csrc/kernels/gf_gemm16.hip): the same header and pointer arrays (rows are
 // byte rows holding little-endian 16-bit symbols), and FOUR records per coefficient, tab[j][i][q]
 // with q = 2 * src_byte + dst_byte (gfrs/gf65536.h perm_quad).

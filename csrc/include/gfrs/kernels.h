@@ -115,7 +115,26 @@ hipError_t launch_gf_update(const void* desc, int d, int m_pad, int64_t col0, in
 hipError_t launch_gf_update_batched(const void* desc, int k, int d, int m_pad, int batch, int64_t col0, int64_t ncols,
                                     bool pairs, bool store_new, bool force_bytewise, hipStream_t stream);
 
-// ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip) ---------------------------------------
+// ---- batched repair (csrc/kernels/gf_repair.hip) -----------------------------------------------
+// `batch` stripes of one shape per launch (grid.y = stripe; more than 65,535 stripes run as several
+// launches that advance in, out and pat and share the table block), each rewriting up to m_pad of its
+// rows from k of its other rows under an erasure pattern of its own: over byte columns [0, ncols),
+// out_i = XOR_j L_q[i][j](in_j) with q = pat[b]. desc: a repair_batch_layout(k, m_pad, batch, npat)
+// record (gfrs/desc.h): stripe b's survivor rows at in_ptr[b*k + j], the rows it rewrites at
+// out_ptr[b*m_pad + i] (0 = padding or fewer erasures than m_pad: never stored, and a tile of such rows
+// is skipped), its pattern at pat[b], and npat table blocks tab[q][j][i] = the map of coeff_q[i][j],
+// m_pad = pad_m(the most erasures of any pattern). pat[b] in [0, npat) is the caller's duty: it is
+// device data, and the kernel forms the table address from it unchecked. One lane per 16-byte group,
+// the ragged tail on extra lanes of the same launch; force_bytewise (any row of any stripe not
+// 16-byte aligned) puts the whole batch on the byte-per-lane form. Rows may be longer than 2^32
+// bytes and stripes further apart. No row written may overlap any other row the batch uses.
+// hipErrorInvalidValue, and nothing launched, for a null desc, batch < 1, npat < 1, k outside
+// [1, 256], an m_pad that pad_m does not produce or above 256, or ncols < 0; ncols == 0 succeeds
+// without a launch.
+hipError_t launch_gf_repair_batched(const void* desc, int k, int m_pad, int batch, int npat, int64_t ncols,
+                                    bool force_bytewise, hipStream_t stream);
+
+// ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip)---------------------------------------
 // Inverts `batch` n x n matrices (row-major, contiguous) with row pivoting, one workgroup each,
 // [A|I] resident in LDS. status[b] = 0 ok, 1 singular. n <= 256.
 // If `desc` is non-null, additionally writes the perm tables of rows `sel_rows[0..m)` of each

@@ -111,6 +111,16 @@ inline void bind_common(py::module_& m) {
     r["bytes"] = l.bytes;
     return r;
   }, py::arg("k"), py::arg("d"), py::arg("m_pad"), py::arg("batch"));
+  m.def("repair_batch_layout", [](int k, int m_pad, int batch, int npat) {
+    const gfrs::RepairBatchLayout l = gfrs::repair_batch_layout(k, m_pad, batch, npat);
+    py::dict r;
+    r["in_off"] = l.in_off;
+    r["out_off"] = l.out_off;
+    r["pat_off"] = l.pat_off;
+    r["tab_off"] = l.tab_off;
+    r["bytes"] = l.bytes;
+    return r;
+  }, py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"));
   m.def("desc_layout16", [](int k, int m_pad, int batch) {
     const gfrs::DescLayout l = gfrs::desc_layout16(k, m_pad, batch);
     py::dict d;

@@ -170,6 +170,15 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("k"), py::arg("d"), py::arg("m_pad"), py::arg("batch"), py::arg("col0"),
       py::arg("ncols"), py::arg("pairs"), py::arg("store_new"), py::arg("bytewise"), py::arg("stream") = 0);
   m.def(
+      "repair_batched",
+      [](uint64_t desc, int k, int m_pad, int batch, int npat, int64_t ncols, bool bytewise, uint64_t stream) {
+        check(launch_gf_repair_batched(reinterpret_cast<const void*>(desc), k, m_pad, batch, npat, ncols, bytewise,
+                                       as_stream(stream)),
+              "gf_repair_batched");
+      },
+      py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("ncols"),
+      py::arg("bytewise"), py::arg("stream") = 0);
+  m.def(
       "invert",
       [](uint64_t a, uint64_t a_inv, int n, int batch, uint64_t status, uint64_t desc, uint64_t sel_rows, int mm,
          int m_pad, uint64_t stream) {

@@ -350,3 +350,24 @@ def update_oracle(e: np.ndarray, parity, changed, old, new) -> np.ndarray:
     parity = np.asarray(parity, dtype=np.uint8)
     delta = np.asarray(old, dtype=np.uint8) ^ np.asarray(new, dtype=np.uint8)
     return parity ^ GF256.gemm(e[:, [int(j) for j in changed]], delta)
+
+
+# ---- repair: rewrite erased rows from the first k survivors -----------------------------------------
+def reconstruct_oracle(g: np.ndarray, rows, erased) -> np.ndarray:
+    """Plain numpy repair over GF(2^8): the n-row stripe ``rows`` with rows ``erased`` (any ids in
+    ``[0, n)``, sorted and deduplicated here) recomputed from the first k rows not erased:
+    ``G[erased] . inv(G[survivors]) . rows[survivors]``. ``g`` is the n x k generator. Returns a new
+    array; raises :class:`SingularMatrixError` for a pattern whose survivors do not determine the data
+    and ``ValueError`` when fewer than k rows survive."""
+    g = np.asarray(g, dtype=np.uint8)
+    out = np.array(rows, dtype=np.uint8)
+    n, k = g.shape
+    erased = sorted(set(int(e) for e in erased))
+    if not erased:
+        return out
+    survivors = [i for i in range(n) if i not in erased][:k]
+    if len(survivors) < k:
+        raise ValueError(f"only {len(survivors)} survivors, need k={k}")
+    coeff = GF256.matmul(g[erased], GF256.invert(g[survivors]))
+    out[erased] = GF256.gemm(coeff, out[survivors])
+    return out

@@ -553,6 +553,137 @@ class ReedSolomon:
             self._cpu_gemm(coeff, ins, outs)
         return stripe
 
+    # ---- batched repair (small objects: B stripes per launch, a pattern per stripe) ------------------
+    @staticmethod
+    def _erased_raw(erased, n: int) -> np.ndarray:
+        """``erased`` of :meth:`reconstruct_batch` as an int64 array, 1-D (one list for every stripe) or
+        ``[B, e]`` padded with -1 (a ragged nested list is padded here); ids not yet validated, except
+        those of a ragged list. Anything else raises ``ValueError``."""
+        what = "reconstruct_batch: erased"
+        if isinstance(erased, torch.Tensor):
+            if erased.device.type != "cpu":
+                raise ValueError(f"{what}: ids are validated on the host and must be a CPU tensor, got {erased.device}")
+            if erased.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"{what}: ids must be integers, got {erased.dtype}")
+            a = erased.numpy()
+        else:
+            try:
+                a = np.asarray(erased)
+            except ValueError:  # a ragged nested list
+                a = None
+            if a is None or a.dtype == object:
+                try:
+                    lists = [[int(e) for e in row] for row in erased]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{what}: expected ids, B id sequences or an integer [B, e] array") from None
+                a = np.full((len(lists), max((len(r) for r in lists), default=0)), -1, dtype=np.int64)
+                for b, row in enumerate(lists):
+                    if row and not 0 <= min(row) <= max(row) < n:
+                        raise ValueError(f"{what}: stripe {b}: ids must lie in [0, {n}), got {row}")
+                    a[b, : len(row)] = row
+            elif a.size and a.dtype.kind not in "iu":
+                raise ValueError(f"{what}: ids must be integers, got {a.dtype}")
+        if a.ndim not in (1, 2):
+            raise ValueError(f"{what}: expected ids, B id sequences or an integer [B, e] array, got shape {tuple(a.shape)}")
+        return np.ascontiguousarray(a, dtype=np.int64)
+
+    def _erased_patterns(self, a: np.ndarray, nstripes: int):
+        """The validated patterns of a batch from :meth:`_erased_raw`'s array: (``pat`` int64 ``[B]``, -1
+        for a stripe with nothing erased; the distinct patterns as ``(survivors, erased)`` id tuples,
+        in the order their first stripes come). Ids sorted and deduplicated per stripe, the
+        survivors the first k ids not erased, every pattern solved once (``self._dm`` caches)."""
+        what = "reconstruct_batch: erased"
+        shared = a.ndim == 1
+        if shared:
+            a = a.reshape(1, -1)
+        elif a.shape[0] != nstripes:
+            raise ValueError(f"{what}: {nstripes} stripes but ids for {a.shape[0]}")
+        n = self.n
+        if a.size and (a.min() < -1 or a.max() >= n):
+            b = int(np.nonzero(((a < -1) | (a >= n)).any(axis=1))[0][0])
+            raise ValueError(f"{what}: {'' if shared else f'stripe {b}: '}ids must lie in [0, {n}) (or be the -1 "
+                             f"padding), got {a[b].tolist()}")
+        s = np.where(a < 0, n, a)
+        s.sort(axis=1)
+        s[:, 1:][s[:, 1:] == s[:, :-1]] = n  # (an id listed twice counts once)
+        s.sort(axis=1)
+        count = (s < n).sum(axis=1)
+        if count.size and count.max() > self.p:
+            b = int(np.nonzero(count > self.p)[0][0])
+            raise UnrecoverableError(f"reconstruct_batch: {'every stripe' if shared else f'stripe {b}'} has "
+                                     f"{int(count[b])} erasures {s[b, :count[b]].tolist()}, more than p={self.p}")
+        s = s[:, : int(count.max()) if count.size else 0]
+        index, first = {(): -1}, {}
+        pat = np.empty(s.shape[0], dtype=np.int64)
+        for b, row in enumerate(s.tolist()):
+            er = tuple(e for e in row if e < n)
+            q = index.get(er)
+            if q is None:
+                q = index[er] = len(index) - 1
+                first[er] = b
+            pat[b] = q
+        patterns = []
+        for er, b in first.items():
+            sv = tuple(i for i in range(n) if i not in er)[: self.k]
+            try:
+                self.decode_matrix(sv)
+            except UnrecoverableError as e:
+                raise UnrecoverableError(f"reconstruct_batch: {'the pattern' if shared else f'stripe {b}'} cannot be "
+                                         f"repaired: erased {list(er)} with survivors {list(sv)}: {e}") from None
+            patterns.append((sv, er))
+        return (np.broadcast_to(pat, (nstripes,)) if shared else pat), patterns
+
+    def reconstruct_batch(self, stripes, erased, parity=None, stream: torch.cuda.Stream | None = None):
+        """:meth:`reconstruct` for B stripes of one shape in ONE launch (grid.y = stripe), each stripe
+        with erasures OF ITS OWN: after real failures objects placed over different node sets have
+        lost different chunks, and one by one the repairs of small objects are launch-bound.
+        ``stripes`` / ``parity``: the forms of :meth:`syndrome_mask_batch` (B stripes of n rows of one
+        length C, natives first). ``erased``: a flat sequence of ids shared by every stripe; a
+        sequence of B id sequences of differing lengths (0..p ids each; an empty one leaves its stripe
+        untouched, its rows are not even read); or an integer ``[B, e]`` numpy array or CPU tensor padded
+        with -1 (ids are validated on the host: a CUDA tensor raises ``ValueError``). Per stripe the
+        result is exactly that of ``reconstruct(stripe_b, erased_b)``: ids sorted and deduplicated,
+        the survivors the first k ids not erased, rows ``erased_b`` rewritten in place and no other
+        byte touched. The distinct patterns of the batch are solved once each on the host and the
+        kernel (``csrc/kernels/gf_repair.hip``) picks each stripe's coefficient tables by a pattern
+        index; the plan is cached on the buffers and the ids, so a repeated call is dict lookups and
+        the launch. Raised before a byte is written: ``ValueError`` for bad ids, a wrong B, bad rows,
+        or a row to rewrite that overlaps any other row the batch uses (so also for a stripe listed
+        twice); :class:`UnrecoverableError` for a stripe with more than p erasures or a singular
+        pattern, naming the first such stripe. CPU tensors, and ``gf65536`` on the GPU, loop over the
+        stripes with :meth:`reconstruct`. Returns ``stripes``."""
+        from ..ops.repair import BatchRepairPlan, check_repair_overlap, repair_rows
+
+        batch = StripeBatch(stripes, self.n, parity, self.k)
+        raw = self._erased_raw(erased, self.n)
+        kernel = batch.device.type == "cuda" and not self.wide
+        key = ("repb", batch.key, raw.shape, raw.tobytes()) if kernel else None
+        plan = self._plans.get(key) if kernel else None
+        if plan is not None:  # a repeat call on the same buffers and patterns: dict lookups and the launch
+            plan.run(stream)
+            return stripes
+        pat, patterns = self._erased_patterns(raw, batch.nstripes)
+        keep = pat >= 0
+        if not keep.any() or batch.ncols == 0:
+            return stripes
+        if self.wide and batch.ncols % 2:
+            raise ValueError("GF(2^16) rows hold 16-bit symbols: the rows must be an even byte count")
+        m_pad = max(len(er) for _, er in patterns)
+        check_repair_overlap(*repair_rows(batch.ptrs()[keep], pat[keep], [(sv, er, None) for sv, er in patterns], m_pad),
+                             batch.ncols)
+        if kernel:
+            full = []
+            for sv, er in patterns:
+                coeff = self.gf.matmul(self.G[list(er)], self.decode_matrix(sv)).astype(self.G.dtype)
+                maps = self._maps(coeff)
+                full.append((sv, er, coeff if maps is None else maps))
+            plan = self._plans[key] = BatchRepairPlan(batch, pat, full, check=False)
+            plan.run(stream)
+            return stripes
+        for b in np.nonzero(keep)[0]:
+            self.reconstruct(batch.rows(int(b)), patterns[int(pat[b])][1], stream=stream)
+        return stripes
+
     # ---- scrub -------------------------------------------------------------------------------
     @property
     def H(self) -> np.ndarray:
@@ -663,8 +794,9 @@ class ReedSolomon:
     def heal_batch(self, stripes, parity=None, report: BatchScrubReport | None = None) -> BatchScrubReport:
         """Repair the dirty stripes of a batch in place, each from its own redundancy. Scrubs if no
         ``report`` is given. A dirty stripe that passes :meth:`heal`'s rule (no unlocated column, 1..p
-        suspects) is rewritten with ``reconstruct(stripe_b, erased=suspects_b)``, one call per such
-        stripe; one that fails it is left byte for byte as it was and listed in ``unhealed``. Nothing
+        suspects) is rewritten as ``reconstruct(stripe_b, erased=suspects_b)`` would, all such stripes
+        in ONE :meth:`reconstruct_batch` call; one that fails it, or whose suspects leave a singular
+        decode system, is left byte for byte as it was and listed in ``unhealed``. Nothing
         is raised for it: one bad object does not stop the batch. If anything was rewritten the whole
         batch is scrubbed once more and that second report is returned, else the first; either has
         ``unhealed`` filled in."""
@@ -673,19 +805,20 @@ class ReedSolomon:
         if report is None:
             report = self.scrub_batch(stripes, parity)
         batch = StripeBatch(stripes, self.n, parity, self.k)
-        unhealed, rewritten = [], False
+        unhealed = []
+        erased = np.full((batch.nstripes, self.p), -1, dtype=np.int64)
         for b in report.dirty:
             rep = report.report[b]
             if rep.unlocated > 0 or not rep.suspects or len(rep.suspects) > self.p:
                 unhealed.append(b)
                 continue
-            try:
-                self.reconstruct(batch.rows(b), erased=rep.suspects)
-            except UnrecoverableError:  # (a singular decode system is found before anything is written)
-                unhealed.append(b)
+            sus = sorted(set(int(e) for e in rep.suspects))
+            if not self.is_recoverable([i for i in range(self.n) if i not in sus][: self.k]):
+                unhealed.append(b)  # (a singular decode system: nothing is written)
                 continue
-            rewritten = True
-        if rewritten:
+            erased[b, : len(sus)] = sus
+        if (erased >= 0).any():
+            self.reconstruct_batch(stripes, erased, parity)
             report = self.scrub_batch(stripes, parity)
         report.unhealed = unhealed
         return report

@@ -1,8 +1,9 @@
-"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, parity update."""
+"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, parity update, batched repair."""
 from .gemm import Gemm16Plan, GemmPlan, build_desc, desc_layout, gf_gemm, pad_m, perm_tables_from_coeff, tile_for
 from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_into_plan, gf_invert, invert_into_plan
 from .matrix import decode_matrix, encoding_matrix, gen_matrix_device, generator
 from .random import fill_random_
+from .repair import BatchRepairPlan
 from .rows import PickPart, StripeBatch, as_rows, batch_part, check_parts, stripe_part, stripe_rows
 from .scrub import BatchScrubPlan, BatchScrubReport, ScrubPlan, ScrubReport
 from .update import BatchUpdatePlan, UpdatePlan
@@ -14,5 +15,6 @@ __all__ = [
     "fill_random_",
     "BatchScrubPlan", "BatchScrubReport", "ScrubPlan", "ScrubReport",
     "BatchUpdatePlan", "UpdatePlan",
+    "BatchRepairPlan",
     "PickPart", "StripeBatch", "as_rows", "batch_part", "check_parts", "stripe_part", "stripe_rows",
 ]
