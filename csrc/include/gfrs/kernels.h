@@ -82,6 +82,29 @@ hipError_t launch_gf_locate_batched(const void* desc, int n, int p, int batch, i
                                     int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
                                     uint64_t* counts, hipStream_t stream);
 
+// ---- correct (csrc/kernels/gf_correct.hip) -----------------------------------------------------
+// Error correction per byte column, in place, over the scrub descriptor, mask and loc operand above:
+// every byte column of the column blocks whose mask word is nonzero gets the smallest repair that
+// explains its syndrome s. A weight-1 column (s == e . H[:, j], any chunk j) has stripe[j][c] ^= e;
+// otherwise, with max_errors == 2, the explanations s == e1 . H[:, j1] ^ e2 . H[:, j2] (j1 < j2,
+// e1, e2 != 0) are counted over all pairs and exactly one is applied; any other column, and every
+// bad column when !locatable, is uncorrectable and not written. Only the patched bytes of the
+// named rows are stored. counts (device, zeroed here first): fixed_bytes[n] (bytes changed per
+// chunk), then the weight-1 columns, the weight-2 columns, the uncorrectable columns and the
+// inconsistent columns: n + 4 words. The rows must not overlap each other. hipErrorInvalidValue,
+// with nothing written, for what launch_gf_locate refuses, a null desc, p < 2, max_errors outside
+// {1, 2}, and max_errors == 2 with p < 4 or n > kCorrectMaxPairN (the pair search walks n^2 / 2
+// pairs per column from log tables in LDS; max_errors == 1 works for any n <= 256).
+constexpr int kCorrectMaxPairN = 64;
+hipError_t launch_gf_correct(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
+                             const int32_t* mask, const uint8_t* loc, bool locatable, int max_errors,
+                             uint64_t* counts, hipStream_t stream);
+// Batched form, as launch_gf_locate_batched: stripe b's counts at counts + b * (n + 4); more than
+// 65535 stripes run as several launches.
+hipError_t launch_gf_correct_batched(const void* desc, int n, int p, int batch, int64_t ncols, bool force_bytewise,
+                                     int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
+                                     int max_errors, uint64_t* counts, hipStream_t stream);
+
 // ---- in-place parity update (csrc/kernels/gf_update.hip) ---------------------------------------
 // The parity of a stripe in which d natives changed, from those natives and the parity rows alone:
 // over byte columns [col0, col0 + ncols), parity_i ^= XOR_t L[i][t](x_t) in place, with x_t =

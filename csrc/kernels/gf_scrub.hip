@@ -28,40 +28,16 @@
 #include "gfrs/desc.h"
 #include "gfrs/kernels.h"
 #include "gfrs/perm_device.h"
+#include "gfrs/scrub_device.h"
 #include "gfrs/tune.h"
 
 namespace gfrs {
 namespace {
 
 using namespace permdev;
+using namespace scrubdev;  // syn_cols, the locate span, dispatch_tile and the argument rules (shared with gf_correct.hip)
 
 __constant__ Tables d_tab = make_tables();
-
-// Syndrome accumulators of one lane's column unit: T = uint8_t (one byte column, any alignment;
-// only the low byte of each accumulator is meaningful) or uint32_t (four columns, 4-byte aligned).
-// The row loads are issued 8 at a time before any is used, as gf_gemm.hip's tail_byte does.
-template <int MT, typename T>
-__device__ __forceinline__ void syn_cols(const DescView& d, int n, int m_pad, int i0, int64_t off,
-                                         uint32_t (&acc)[MT]) {
-  constexpr int kB = 8;
-#pragma unroll
-  for (int i = 0; i < MT; ++i) acc[i] = 0;
-  for (int j0 = 0; j0 < n; j0 += kB) {
-    T x[kB];
-#pragma unroll
-    for (int u = 0; u < kB; ++u) x[u] = j0 + u < n ? *(gptr<const T>)(d.in[j0 + u] + uint64_t(off)) : T(0);
-#pragma unroll
-    for (int u = 0; u < kB; ++u) {
-      const int j = j0 + u;
-      if (j < n) {
-        const Sel s = make_sel(x[u]);
-        const auto t = d.tab + (size_t(j) * m_pad + i0) * kPermStride;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) acc[i] = mac_map(acc[i], t + i * kPermStride, s);
-      }
-    }
-  }
-}
 
 // bit i: syndrome row i0 + i is nonzero in this byte column
 template <int MT>
@@ -270,8 +246,6 @@ __global__ __launch_bounds__(kBlock) void gf_syndrome_byte_kernel(DescView d, in
 }
 
 // ---- locate -----------------------------------------------------------------------------------
-constexpr int kLocSpanShift = 14;  // a workgroup covers min(block_bytes, 16 KiB) columns
-
 struct LocLds {
   uint8_t exp[1024];         // gf256.h layout: exp[510..1020] = 0
   uint16_t log[256];         // log[0] = 510
@@ -401,23 +375,6 @@ inline Grid make_grid(int64_t items, int ntiles) {
   return g;
 }
 
-template <typename F>
-hipError_t dispatch_tile(int t, F&& f) {
-  switch (t) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    default: return f(std::integral_constant<int, 16>{});
-  }
-}
-
-inline int log2_exact(int64_t v) {
-  int s = 0;
-  while ((int64_t(1) << s) < v) ++s;
-  return (int64_t(1) << s) == v ? s : -1;
-}
-
 // The rows-in-flight form is built for the (4, 6) and (10, 14) codes, one tile each; `ident` = the
 // trailing identity columns of H, and with ident == MT the parity rows skip the multiplies.
 // GFRS_TUNE=scrub_rows=0 keeps every launch on the general form, scrub_ident=0 multiplies the
@@ -450,11 +407,6 @@ bool launch_rows(const DescView& d, int n, int m_pad, int ident, const Grid& g, 
     }
   }
   return false;
-}
-
-bool scrub_args_ok(int n, int m_pad, int64_t ncols, int64_t block_bytes) {
-  return n >= 1 && n <= 256 && m_pad >= 1 && m_pad % tile_for(m_pad) == 0 && ncols >= 0 && block_bytes >= 4096 &&
-         log2_exact(block_bytes) > 0;
 }
 
 // One syndrome launch over `batch` stripes (grid.y); `d` and `mask` are those of the first of them.
@@ -494,14 +446,6 @@ hipError_t locate_launch(const DescView& d, int n, int p, unsigned batch, int64_
     return hipGetLastError();
   });
 }
-
-bool locate_args_ok(int n, int p, int64_t ncols, int64_t block_bytes) {
-  if (p < 1 || p > 16 || p >= n || !scrub_args_ok(n, pad_m(p), ncols, block_bytes)) return false;
-  const int span_shift = std::min(log2_exact(block_bytes), kLocSpanShift);
-  return ((ncols + (int64_t(1) << span_shift) - 1) >> span_shift) <= int64_t(INT32_MAX);
-}
-
-constexpr int kMaxGridY = 65535;  // stripes per launch, as launch_gf_gemm_batched
 
 }  // namespace
 

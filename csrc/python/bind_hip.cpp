@@ -150,6 +150,31 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("block_bytes"), py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("counts"),
       py::arg("stream") = 0);
   m.def(
+      "correct",
+      [](uint64_t desc, int n, int p, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask, uint64_t loc,
+         bool locatable, int max_errors, uint64_t counts, uint64_t stream) {
+        check(launch_gf_correct(reinterpret_cast<const void*>(desc), n, p, ncols, bytewise, block_bytes,
+                                reinterpret_cast<const int32_t*>(mask), reinterpret_cast<const uint8_t*>(loc),
+                                locatable, max_errors, reinterpret_cast<uint64_t*>(counts), as_stream(stream)),
+              "gf_correct");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("p"), py::arg("ncols"), py::arg("bytewise"), py::arg("block_bytes"),
+      py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("max_errors"), py::arg("counts"),
+      py::arg("stream") = 0);
+  m.def(
+      "correct_batched",
+      [](uint64_t desc, int n, int p, int batch, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask,
+         uint64_t loc, bool locatable, int max_errors, uint64_t counts, uint64_t stream) {
+        check(launch_gf_correct_batched(reinterpret_cast<const void*>(desc), n, p, batch, ncols, bytewise, block_bytes,
+                                        reinterpret_cast<const int32_t*>(mask), reinterpret_cast<const uint8_t*>(loc),
+                                        locatable, max_errors, reinterpret_cast<uint64_t*>(counts),
+                                        as_stream(stream)),
+              "gf_correct_batched");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("p"), py::arg("batch"), py::arg("ncols"), py::arg("bytewise"),
+      py::arg("block_bytes"), py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("max_errors"),
+      py::arg("counts"), py::arg("stream") = 0);
+  m.def(
       "update",
       [](uint64_t desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs, bool store_new, bool bytewise,
          uint64_t stream) {

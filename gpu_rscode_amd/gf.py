@@ -340,6 +340,75 @@ def scrub_oracle(h: np.ndarray, rows, block_bytes: int = 65536):
     return mask, votes, int(pending.sum()), bad_columns
 
 
+# ---- correct: error correction per byte column -----------------------------------------------------
+def correct_oracle(h: np.ndarray, rows, max_errors: int):
+    """Plain numpy error correction of an n-row stripe against the check matrix ``h`` (p x n), one
+    byte column at a time: returns ``(fixed_rows, fixed_bytes[n], by_weight[3], uncorrectable,
+    bad_columns)``; ``rows`` is not modified.
+
+    A column with syndrome ``s = h . rows[:, c] != 0`` is repaired with the smallest set of chunks
+    that explains it. When p < 2 or the columns of ``h`` are not pairwise independent it is
+    uncorrectable. Otherwise, if ``s = e . h[:, j]`` for a chunk j and e != 0 (then unique), byte
+    ``rows[j][c]`` gets ``^= e`` (weight 1). Otherwise, with ``max_errors == 2``, every pair j1 < j2
+    is solved for ``s = e1 . h[:, j1] ^ e2 . h[:, j2]`` on a nonsingular 2 x 2 row minor and checked
+    on all p rows with e1, e2 != 0: exactly one such explanation over all pairs is applied (weight
+    2); none, or more than one, leaves the column uncorrectable and byte for byte as it was.
+    ``fixed_bytes[j]`` counts the bytes changed in chunk j, ``by_weight[w]`` the columns corrected
+    with w errors (``by_weight[0]`` stays 0)."""
+    if max_errors not in (1, 2):
+        raise ValueError(f"max_errors must be 1 or 2, got {max_errors}")
+    h = np.asarray(h, dtype=np.uint8)
+    p, n = h.shape
+    out = np.array(np.stack([np.asarray(r, dtype=np.uint8) for r in rows]) if not isinstance(rows, np.ndarray)
+                   else rows, dtype=np.uint8)
+    fixed_bytes, by_weight = np.zeros(n, dtype=np.int64), np.zeros(3, dtype=np.int64)
+    bad = np.nonzero(GF256.gemm(h, out).any(axis=0))[0]
+    if bad.size == 0:
+        return out, fixed_bytes, by_weight, 0, 0
+    if p < 2 or not columns_independent(h):
+        return out, fixed_bytes, by_weight, int(bad.size), int(bad.size)
+    mul = np.stack([GF256.mul_table(c) for c in range(256)])  # mul[a][b]
+    inv = np.zeros(256, dtype=np.int64)
+    inv[1:] = GF256.inv(np.arange(1, 256))
+    s = GF256.gemm(h, out[:, bad])  # p x m: the bad columns only
+    pending = np.ones(bad.size, dtype=bool)
+    for j in range(n):
+        r = int(np.nonzero(h[:, j])[0][0])
+        e = mul[inv[h[r, j]]][s[r]]
+        hit = pending & (e != 0) & (mul[h[:, j][:, None], e[None, :]] == s).all(axis=0)
+        out[j, bad[hit]] ^= e[hit]
+        fixed_bytes[j] += int(hit.sum())
+        pending &= ~hit
+    by_weight[1] = int((~pending).sum())
+    if max_errors == 2 and pending.any():
+        todo = np.nonzero(pending)[0]
+        st = s[:, todo]
+        count = np.zeros(todo.size, dtype=np.int64)
+        found = np.zeros((4, todo.size), dtype=np.int64)  # j1, j2, e1, e2 of a column's first explanation
+        for j1, j2 in itertools.combinations(range(n), 2):
+            a, b = next((a, b) for a, b in itertools.combinations(range(p), 2)
+                        if mul[h[a, j1], h[b, j2]] != mul[h[a, j2], h[b, j1]])  # (pairwise independent: there is one)
+            idet = inv[mul[h[a, j1], h[b, j2]] ^ mul[h[a, j2], h[b, j1]]]
+            e1 = mul[idet][mul[h[b, j2]][st[a]] ^ mul[h[a, j2]][st[b]]]  # Cramer's rule, characteristic 2
+            e2 = mul[idet][mul[h[b, j1]][st[a]] ^ mul[h[a, j1]][st[b]]]
+            ok = (e1 != 0) & (e2 != 0)
+            ok &= ((mul[h[:, j1][:, None], e1[None, :]] ^ mul[h[:, j2][:, None], e2[None, :]]) == st).all(axis=0)
+            first = ok & (count == 0)
+            found[:, first] = np.stack([np.full(int(first.sum()), j1), np.full(int(first.sum()), j2),
+                                        e1[first], e2[first]])
+            count += ok
+        for x in np.nonzero(count == 1)[0]:
+            j1, j2, e1, e2 = (int(v) for v in found[:, x])
+            c = bad[todo[x]]
+            out[j1, c] ^= e1
+            out[j2, c] ^= e2
+            fixed_bytes[j1] += 1
+            fixed_bytes[j2] += 1
+        by_weight[2] = int((count == 1).sum())
+        pending[todo[count == 1]] = False
+    return out, fixed_bytes, by_weight, int(pending.sum()), int(bad.size)
+
+
 # ---- partial-stripe writes: the delta identity -----------------------------------------------------
 def update_oracle(e: np.ndarray, parity, changed, old, new) -> np.ndarray:
     """Plain numpy parity update over GF(2^8): the parity rows of the stripe in which natives

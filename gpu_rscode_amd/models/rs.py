@@ -20,6 +20,8 @@ import torch
 
 from .. import gf
 from .._native import cpu, hip
+from ..ops.correct import (BatchCorrectPlan, BatchCorrectReport, CorrectPlan, CorrectReport, check_disjoint,
+                           check_max_errors, cpu_correct, make_batch_correct_report)
 from ..ops.gemm import Gemm16Plan, GemmPlan
 from ..ops.inverse import decode16_device_supported, decode_system16_into_plan, decode_system_into_plan
 from ..ops.matrix import decode_matrix, encoding_matrix
@@ -822,6 +824,90 @@ class ReedSolomon:
             report = self.scrub_batch(stripes, parity)
         report.unhealed = unhealed
         return report
+
+    # ---- correct: error correction per byte column ---------------------------------------------
+    def _correct(self, what: str, batched: bool, stripes, parity, max_errors, block_bytes: int, stream):
+        """The call behind :meth:`correct` and :meth:`correct_batch`: everything is validated before
+        anything is launched or written; then a cached plan on the GPU, or the CPU form stripe by stripe."""
+        if self.field != "gf256":
+            raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
+        if batched:
+            batch = StripeBatch(stripes, self.n, parity, self.k)
+            nstripes, ncols, dev = batch.nstripes, batch.ncols, batch.device
+        else:
+            rows, ncols, dev = stripe_rows(stripes, self.n)
+            nstripes = 1
+        block_bytes = check_block_bytes(block_bytes)
+        max_errors = check_max_errors(max_errors, self.p, self.n)
+        if dev.type == "cuda" and nstripes > 0 and (ncols > 0 or not batched):
+            key = (("correctb", block_bytes, max_errors) + batch.key if batched
+                   else self._key(("correct", block_bytes, max_errors), rows))
+            plan = self._plans.get(key)
+            if plan is None:
+                # (the plan runs the aliasing check: a key names the rows' addresses and lengths, so a hit
+                # is for rows that passed it)
+                plan = (BatchCorrectPlan(batch, self.H, max_errors, block_bytes) if batched
+                        else CorrectPlan(rows, self.H, max_errors, block_bytes))
+                self._plans[key] = plan
+            return plan.correct(stream)
+        if batched:
+            check_disjoint(batch.ptrs(), ncols)
+        else:
+            check_disjoint(np.array([[r.data_ptr() for r in rows]], dtype=np.uint64),
+                           np.array([[r.numel() for r in rows]], dtype=np.int64))
+        nmask = -(-ncols // block_bytes)
+        mask = torch.zeros((nstripes, nmask), dtype=torch.int32, device=dev)
+        fixed, by_weight = np.zeros((nstripes, self.n), dtype=np.int64), np.zeros((nstripes, 3), dtype=np.int64)
+        unc, bad = np.zeros(nstripes, dtype=np.int64), np.zeros(nstripes, dtype=np.int64)
+        if dev.type != "cuda" and nmask:
+            h = self.H
+            for b in range(nstripes):
+                mask[b], fixed[b], by_weight[b], unc[b], bad[b] = cpu_correct(
+                    h, batch.rows(b) if batched else rows, ncols, block_bytes, max_errors, self._cpu_gemm)
+        report = make_batch_correct_report(fixed, by_weight, unc, bad, mask)
+        return report if batched else report.report[0]
+
+    def correct(self, stripe, max_errors: int | None = None, block_bytes: int = 65536,
+                stream: torch.cuda.Stream | None = None) -> CorrectReport:
+        """Repair silent corruption in place, one byte column at a time: where :meth:`heal` names
+        suspect chunks and rewrites them whole (and gives up past p suspects, or when two chunks are
+        wrong in one column), this XORs the error values into the wrong bytes alone. ``stripe`` as
+        for :meth:`scrub`. For every column with a nonzero syndrome ``s``:
+
+        * weight 1: ``s = e . H[:, j]`` for one chunk j (natives and parity alike): ``stripe[j][c] ^= e``;
+        * else, with ``max_errors=2``: the explanations ``s = e1 . H[:, j1] ^ e2 . H[:, j2]`` are
+          counted over all pairs of chunks; exactly one is applied, none or more than one (the
+          reference Vandermonde matrix is not MDS: some 4-sets of its check columns are dependent)
+          leaves the column **uncorrectable**, byte for byte as it was.
+
+        Returns a :class:`~gpu_rscode_amd.ops.correct.CorrectReport`: ``fixed_bytes[j]`` bytes changed
+        in chunk j, ``by_weight[w]`` columns corrected with w errors, ``uncorrectable`` columns left,
+        ``mask`` the syndrome mask before correction. On the GPU: the syndrome launch, one correct
+        launch over the dirty blocks, one sync. ``uncorrectable == 0`` means the stripe is consistent
+        afterwards. Nothing but the patched bytes is written.
+
+        ``max_errors`` defaults to ``min(2, p // 2)``; 2 needs p >= 4 (distance 5), else
+        ``ValueError``, as for p < 2 and for a stripe in which any row overlaps another. Limits:
+        GF(2^8) only, p <= 16 and, for ``max_errors=2``, n <= 64 (``ops.correct.MAX_PAIR_N``), else
+        ``NotImplementedError``; ``max_errors=1`` works for any n <= 256. Every refusal leaves the
+        buffers unchanged.
+
+        More wrong chunks in a column than ``max_errors`` are beyond the code: most such columns are
+        uncorrectable, but three or more errors can imitate a pattern of weight one or two, and the
+        column is then "corrected" into a consistent but wrong one (with p = 2 and
+        ``max_errors=1`` a double error already can, as in :meth:`heal`). That is inherent to the
+        code's distance, not to this decoder."""
+        return self._correct("correct", False, stripe, None, max_errors, block_bytes, stream)
+
+    def correct_batch(self, stripes, parity=None, max_errors: int | None = None, block_bytes: int = 65536,
+                      stream: torch.cuda.Stream | None = None) -> BatchCorrectReport:
+        """:meth:`correct` for B stripes of one shape (the forms of :meth:`syndrome_mask_batch`): on
+        the GPU one launch of each kernel and one sync for the whole batch. Returns a
+        :class:`~gpu_rscode_amd.ops.correct.BatchCorrectReport`, whose ``report[b]`` equals what
+        :meth:`correct` returns for stripe b alone. No row may overlap another row of any stripe (a
+        stripe listed twice is refused): ``ValueError`` before anything is written. The limits are
+        :meth:`correct`'s."""
+        return self._correct("correct_batch", True, stripes, parity, max_errors, block_bytes, stream)
 
     # ---- partial-stripe writes ----------------------------------------------------------------
     def _update_rows(self, what: str, changed, parity, first, second):

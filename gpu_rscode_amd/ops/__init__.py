@@ -1,4 +1,5 @@
-"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, parity update, batched repair."""
+"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, correct, parity update, batched repair."""
+from .correct import BatchCorrectPlan, BatchCorrectReport, CorrectPlan, CorrectReport
 from .gemm import Gemm16Plan, GemmPlan, build_desc, desc_layout, gf_gemm, pad_m, perm_tables_from_coeff, tile_for
 from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_into_plan, gf_invert, invert_into_plan
 from .matrix import decode_matrix, encoding_matrix, gen_matrix_device, generator
@@ -14,6 +15,7 @@ __all__ = [
     "gen_matrix_device", "generator",
     "fill_random_",
     "BatchScrubPlan", "BatchScrubReport", "ScrubPlan", "ScrubReport",
+    "BatchCorrectPlan", "BatchCorrectReport", "CorrectPlan", "CorrectReport",
     "BatchUpdatePlan", "UpdatePlan",
     "BatchRepairPlan",
     "PickPart", "StripeBatch", "as_rows", "batch_part", "check_parts", "stripe_part", "stripe_rows",

@@ -23,7 +23,7 @@ from .rows import StripeBatch, stripe_part
 
 MIN_BLOCK_BYTES = 4096
 MAX_LOCATE_P = 16  # the locate kernel keeps one output tile of syndrome bytes per lane
-_CPU_STEP = 1 << 20  # columns per syndrome slice of the CPU form (p scratch rows of this length)
+CPU_STEP = 1 << 20  # columns per syndrome slice of the CPU form (p scratch rows of this length)
 
 
 @dataclass
@@ -122,7 +122,7 @@ def make_batch_report(votes: np.ndarray, unlocated: np.ndarray, bad_columns: np.
                             np.asarray(votes, dtype=np.int64), mask, [int(b) for b in np.nonzero(bad_columns)[0]], [])
 
 
-class _Scrub:
+class ScrubBase:
     """What :class:`ScrubPlan` and :class:`BatchScrubPlan` share: everything but how they are built and
     whether the launches and results carry a stripe axis (``_batched``)."""
 
@@ -189,7 +189,7 @@ class _Scrub:
         return report(host[..., : self.n].copy(), host[..., self.n].copy(), host[..., self.n + 1].copy(), mask)
 
 
-class ScrubPlan(_Scrub):
+class ScrubPlan(ScrubBase):
     """A reusable device scrub of one stripe's buffers, as ``GemmPlan(hold_buffers=False)``: it keeps
     raw row pointers only, so a cache may hand it out only for the caller's live tensors.
 
@@ -207,7 +207,7 @@ class ScrubPlan(_Scrub):
         self._build(part, part.nrows, h, block_bytes)
 
 
-class BatchScrubPlan(_Scrub):
+class BatchScrubPlan(ScrubBase):
     """A reusable device scrub of B stripes of one shape, one launch per kernel (grid.y = stripe). As
     :class:`ScrubPlan` it keeps raw row pointers only, so a cache may hand it out only for the
     caller's live tensors.
@@ -228,7 +228,7 @@ class BatchScrubPlan(_Scrub):
 
 
 @lru_cache(maxsize=1)
-def _mul_table() -> np.ndarray:
+def mul_table() -> np.ndarray:
     """mul[a][b] over GF(2^8) (64 KiB)."""
     return np.stack([gf.GF256.mul_table(c) for c in range(256)])
 
@@ -264,8 +264,8 @@ def cpu_scrub(h: np.ndarray, rows: list[torch.Tensor], ncols: int, block_bytes: 
     if p == 0 or ncols == 0:
         return torch.from_numpy(bits.view(np.int32)), votes, 0, 0
     locatable, piv, unit = _cpu_locator(h.tobytes(), p, n)
-    mul = _mul_table()
-    step = min(_CPU_STEP, -(-ncols // 64) * 64)
+    mul = mul_table()
+    step = min(CPU_STEP, -(-ncols // 64) * 64)
     scratch = torch.empty((p, step), dtype=torch.uint8)
     for c0 in range(0, ncols, step):
         c1 = min(ncols, c0 + step)

@@ -26,6 +26,18 @@ each timed with device events over a window of ``--reps`` calls (a call of (b) i
 its window holds ``--reps`` / 8 of them), and, for (a) and (b), by the host clock around the same
 window ended by a synchronise: launch gaps are what the batched call removes. Then ``scrub_batch``
 on the clean batch and with one chunk of one stripe overwritten.
+
+``--correct`` measures error correction per byte column against the calls it stands next to, at the
+same shape (with ``--batch B``: B stripes per call, the ``_batch`` forms). In interleaved rounds of
+one call each, timed with device events around the call (its one sync included):
+
+  * ``scrub`` and ``correct`` on the clean stripe (``correct`` launches what ``scrub`` launches there);
+  * with one byte wrong in every 4 KiB of one chunk: ``scrub``, ``correct`` and ``heal`` (which
+    rebuilds the whole chunk and scrubs twice);
+  * with two whole chunks overwritten, the pair search on every column: ``correct`` next to
+    ``reconstruct`` of those two chunks as erasures.
+
+A call that repairs is handed a freshly damaged stripe every time; the damage is not timed.
 """
 from __future__ import annotations
 
@@ -50,6 +62,7 @@ def parse_args(argv=None):
     ap.add_argument("--reps", type=int, default=40, help="calls per timed window")
     ap.add_argument("--scrub-reps", type=int, default=10)
     ap.add_argument("--batch", type=int, default=0, help="B > 0: the batched scrub of B stripes of --cols bytes")
+    ap.add_argument("--correct", action="store_true", help="time correct next to scrub, heal and reconstruct")
     ap.add_argument("--out", default=None, help="also write the JSON here")
     return ap.parse_args(argv)
 
@@ -159,6 +172,102 @@ def main_batch(args) -> int:
     return 0
 
 
+def main_correct(args) -> int:
+    import torch
+
+    from gpu_rscode_amd import ReedSolomon
+    from gpu_rscode_amd.models.rs import row_pitch
+    from gpu_rscode_amd.ops import fill_random_
+
+    k, n, C, bb, B = args.k, args.n, args.cols, args.block_bytes, max(1, args.batch)
+    p = n - k
+    batched = args.batch > 0
+    rs = ReedSolomon(k, n, matrix=args.matrix)
+    pitch = row_pitch(C, "cuda")
+    base = torch.empty(B * n * pitch, dtype=torch.uint8, device="cuda")
+    fill_random_(base, seed=1)
+    stripes = base.as_strided((B, n, C), (n * pitch, pitch, 1))
+    rs.encode_batch(stripes[:, :k], stripes[:, k:])
+    arg = stripes if batched else stripes[0]
+    scrub = (lambda: rs.scrub_batch(arg, block_bytes=bb)) if batched else (lambda: rs.scrub(arg, bb))
+    correct = (lambda: rs.correct_batch(arg, block_bytes=bb)) if batched else (lambda: rs.correct(arg, block_bytes=bb))
+    heal = (lambda: rs.heal_batch(arg)) if batched else (lambda: rs.heal(arg))
+    va, vb = min(3, k - 1), n - 2  # a native and a parity chunk
+
+    def reconstruct():
+        return rs.reconstruct_batch(arg, [va, vb]) if batched else rs.reconstruct(arg, erased=[va, vb])
+
+    def timed(fn) -> float:
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        s.record()
+        fn()
+        t.record()
+        t.synchronize()
+        return s.elapsed_time(t)
+
+    def rounds(calls: dict, count: int, before=None) -> dict:
+        times = {name: [] for name in calls}
+        for _ in range(count):
+            for name, fn in calls.items():
+                if before is not None:
+                    before()
+                times[name].append(timed(fn))
+        return times
+
+    def all_clean(rep) -> bool:
+        return bool(rep.clean.all()) if batched else rep.clean
+
+    res = {"shape": {"k": k, "n": n, "matrix": args.matrix, "cols": C, "block_bytes": bb, "batch": args.batch},
+           "rounds": args.rounds, "damaged_rounds": args.scrub_reps, "device": torch.cuda.get_device_name(0)}
+    assert all_clean(scrub()) and all_clean(correct())
+    rounds({"scrub": scrub, "correct": correct}, 2)  # warm-up
+    clean = rounds({"scrub": scrub, "correct": correct}, args.rounds)
+    res["clean"] = {name: spread(ms) for name, ms in clean.items()}
+    res["clean"]["correct_median_above_scrub_max"] = bool(statistics.median(clean["correct"]) > max(clean["scrub"]))
+
+    good = stripes[:, [va, vb]].clone()
+
+    def restore():
+        stripes[:, va].copy_(good[:, 0])
+        stripes[:, vb].copy_(good[:, 1])
+
+    def scatter():  # one byte wrong in every 4 KiB of chunk va
+        restore()
+        stripes[:, va, ::4096] ^= 0x5A
+
+    scatter()
+    rep = correct()
+    per_stripe = -(-C // 4096)
+    assert int(rep.uncorrectable.sum() if batched else rep.uncorrectable) == 0
+    assert int(rep.by_weight[..., 1].sum()) == B * per_stripe and all_clean(scrub())
+    scatter()
+    assert all_clean(heal()) and torch.equal(stripes[:, va], good[:, 0])
+    times = rounds({"scrub": scrub, "correct": correct, "heal": heal}, args.scrub_reps, before=scatter)
+    res["one_byte_per_4k_of_one_chunk"] = {name: spread(ms) for name, ms in times.items()}
+    res["one_byte_per_4k_of_one_chunk"]["wrong_bytes"] = B * per_stripe
+
+    def overwrite():  # two whole chunks replaced by random bytes
+        for b in range(B):
+            fill_random_(stripes[b, va][: C // 16 * 16], seed=98 + 2 * b)
+            fill_random_(stripes[b, vb][: C // 16 * 16], seed=99 + 2 * b)
+
+    if p >= 4:
+        overwrite()
+        rep = correct()
+        res["two_chunks_overwritten"] = {"by_weight": [int(v) for v in rep.by_weight.reshape(-1, 3).sum(axis=0)],
+                                         "uncorrectable": int(rep.uncorrectable.sum() if batched else rep.uncorrectable)}
+        overwrite()
+        reconstruct()
+        assert torch.equal(stripes[:, [va, vb]], good)
+        times = rounds({"correct": correct, "reconstruct": reconstruct}, args.scrub_reps, before=overwrite)
+        res["two_chunks_overwritten"].update({name: spread(ms) for name, ms in times.items()})
+    restore()
+    assert all_clean(scrub())
+    emit(res, args.out)
+    return 0
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -169,6 +278,8 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         print("scrub_bench.py needs a GPU", file=sys.stderr)
         return 2
+    if args.correct:
+        return main_correct(args)
     if args.batch > 0:
         return main_batch(args)
     k, n, C, bb = args.k, args.n, args.cols, args.block_bytes
