@@ -105,7 +105,10 @@ class _PlanCache(OrderedDict):
     """Plans keyed by (op, buffers, pattern), least recently used evicted past ``capacity``. The
     plans hold no references to the buffers (``hold_buffers=False``): a key names the exact row
     pointers, so a hit only happens for the caller's live tensors, and a loop over fresh buffers
-    does not keep up to ``capacity`` generations of them allocated. A hit
+    does not keep up to ``capacity`` generations of them allocated. A hit runs the plan unexamined, so
+    a key names everything the plan was built from: pointer, shape and strides of every tensor (or
+    pointer and length of every row), inputs and outputs alike, the ids and the options (docs/API.md;
+    tests/test_gpu_plan_cache.py tries each with two calls at one base pointer). A hit
     must never turn into a rebuild while a caller relies on the plan: a hipGraph capture of
     ``encode_batch`` after 64 per-object ``encode`` calls used to miss because the old cache was
     cleared wholesale past 64 entries (and building a plan uploads a descriptor, which a capturing
@@ -331,7 +334,9 @@ class ReedSolomon:
             for b in range(B):
                 self.encode(data[b], parity[b])
             return parity
-        key = ("encb", int(data.data_ptr()), tuple(data.stride()), tuple(data.shape), int(parity.data_ptr()))
+        # (the plan holds the parity rows' addresses and their batch stride: the key names them too)
+        key = ("encb", int(data.data_ptr()), tuple(data.stride()), tuple(data.shape), int(parity.data_ptr()),
+               tuple(parity.stride()), tuple(parity.shape))
         plan = self._plans.get(key)
         if plan is None:
             if self.wide:  # GF(2^16): matrix cores for stripes at fixed strides, else batched v_perm
@@ -370,7 +375,7 @@ class ReedSolomon:
                 self._cpu_gemm(dm, as_rows(survivors[b]), [out[b, i] for i in erased])
             return out
         key = ("decb", tuple(rows), int(survivors.data_ptr()), tuple(survivors.stride()), tuple(survivors.shape),
-               int(out.data_ptr()), tuple(out.stride()))
+               int(out.data_ptr()), tuple(out.stride()), tuple(out.shape))
         plan = self._plans.get(key)
         if plan is None:
             outs = [[out[b, i] for i in erased] for b in range(B)]

@@ -131,7 +131,9 @@ class ListPart:
 
     @property
     def key(self) -> tuple:
-        return ("l", self.lens if isinstance(self.lens, int) else self.lens.tobytes(), self._ptrs.tobytes())
+        # (the [B, r] shape too: two stripes of three rows and three of two have the same pointer bytes)
+        return ("l", self._ptrs.shape, self.lens if isinstance(self.lens, int) else self.lens.tobytes(),
+                self._ptrs.tobytes())
 
     def ptrs(self) -> np.ndarray:
         return self._ptrs
@@ -142,7 +144,9 @@ class ListPart:
 
 class PickPart:
     """Rows ``idx[b, t]`` of stripe b of another part of one row length (or of a ``StripeBatch``): the
-    changed natives of a batched write, or its parity rows."""
+    changed natives of a batched write, or its parity rows. ``key`` names the source, the ``[B, r]`` shape
+    of the ids and their bytes; a ``tag`` stands in for the bytes, and is the caller's promise that
+    within one plan cache the tag and the shape determine the ids (the parity rows ``k..n-1`` of a codec)."""
 
     ragged = False
 
@@ -150,7 +154,7 @@ class PickPart:
         self.src, self.idx = src, np.ascontiguousarray(idx, dtype=np.int64)
         self.nstripes, self.nrows = (int(v) for v in self.idx.shape)
         self.ncols, self.lens, self.device = src.ncols, src.ncols, src.device
-        self.key = ("p", src.key, tag if tag is not None else self.idx.tobytes())
+        self.key = ("p", src.key, self.idx.shape, tag if tag is not None else self.idx.tobytes())
 
     def ptrs(self) -> np.ndarray:
         return np.take_along_axis(self.src.ptrs(), self.idx, axis=1)
