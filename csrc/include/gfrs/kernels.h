@@ -105,6 +105,39 @@ hipError_t launch_gf_correct_batched(const void* desc, int n, int p, int batch, 
                                      int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
                                      int max_errors, uint64_t* counts, hipStream_t stream);
 
+// ---- checked repair (csrc/kernels/gf_checked.hip) ----------------------------------------------
+// Errors-and-erasures repair of a degraded stripe: e erased rows are rebuilt from the first
+// k = ns - r of the ns survivors while the other r survivors check them, in one pass. desc: a
+// desc_layout(ns, pad_m(e + r)) descriptor whose inputs are the ns survivor rows in ascending chunk
+// order, whose out_ptr[0..e) are the erased rows (every other entry 0) and whose tables are those of
+// T[:, S] ((e + r) x ns; T = inv(H[:, X + R]) . H: rows 0..e-1 rebuild, rows e..e+r-1 are [B | I_r]).
+// launch_gf_checked stores out_i = T[i, S] . survivors for i < e over byte columns [0, ncols) and
+// sets bit t of mask[b] when check row e + t is nonzero anywhere in column block b (mask zeroed here
+// first, ceil(ncols / block_bytes) words). The erased rows are never read; a consistent stripe moves
+// ns rows in, e rows out and nothing else. e = 0 only checks; r = 0 only rebuilds (mask stays zero).
+// launch_gf_checked_fix (r >= 1) then runs launch_gf_correct's rule over the dirty blocks with the
+// r x ns check matrix T[e:, S] on the survivors: loc = launch_gf_locate's operand for that matrix,
+// followed by T[:e, S] row-major (e x ns bytes). A corrected survivor byte j gets ^= v and every
+// erased row i ^= v . T[i][j]; an uncorrectable column is not written. counts (zeroed here first):
+// fixed_bytes[ns] by survivor index, then weight-1, weight-2, uncorrectable and bad columns. No row
+// may overlap another. hipErrorInvalidValue, with nothing written, for a null pointer, e < 0, r < 0,
+// e + r outside [1, 16], r >= ns, ns > 256, a bad ncols or block_bytes (as launch_gf_syndrome), and in
+// the fix launchers r < 1, max_errors outside {1, 2} and max_errors == 2 with r < 4 or
+// ns > kCorrectMaxPairN. Batched forms: desc_layout(ns, pad_m(e + r), batch), stripe b's rows at
+// in_ptr[b * ns + j] and out_ptr[b * pad_m(e + r) + i], one T for the batch, mask and counts rows
+// per stripe as the scrub launchers; more than 65535 stripes run as several launches.
+hipError_t launch_gf_checked(const void* desc, int ns, int e, int r, int64_t ncols, bool force_bytewise,
+                             int64_t block_bytes, int32_t* mask, hipStream_t stream);
+hipError_t launch_gf_checked_batched(const void* desc, int ns, int e, int r, int batch, int64_t ncols,
+                                     bool force_bytewise, int64_t block_bytes, int32_t* mask, hipStream_t stream);
+hipError_t launch_gf_checked_fix(const void* desc, int ns, int e, int r, int64_t ncols, bool force_bytewise,
+                                 int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
+                                 int max_errors, uint64_t* counts, hipStream_t stream);
+hipError_t launch_gf_checked_fix_batched(const void* desc, int ns, int e, int r, int batch, int64_t ncols,
+                                         bool force_bytewise, int64_t block_bytes, const int32_t* mask,
+                                         const uint8_t* loc, bool locatable, int max_errors, uint64_t* counts,
+                                         hipStream_t stream);
+
 // ---- in-place parity update (csrc/kernels/gf_update.hip) ---------------------------------------
 // The parity of a stripe in which d natives changed, from those natives and the parity rows alone:
 // over byte columns [col0, col0 + ncols), parity_i ^= XOR_t L[i][t](x_t) in place, with x_t =

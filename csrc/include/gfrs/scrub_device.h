@@ -1,6 +1,7 @@
-// What the cold-path kernels over a scrub descriptor share (gf_scrub.hip's locate, gf_correct.hip):
-// the per-lane syndrome of a column unit, the workgroup span, the tile dispatch and the argument
-// rules of their launchers. Include from a .hip file only.
+// What the kernels over a scrub descriptor share (gf_scrub.hip, gf_correct.hip, gf_checked.hip): the
+// per-lane syndrome of a column unit, the hot pass's fold of row bits into the mask and its grid,
+// the workgroup span, the tile dispatch and the argument rules of their launchers. Include from a
+// .hip file only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +41,52 @@ __device__ __forceinline__ void syn_cols(const DescView& d, int n, int m_pad, in
       }
     }
   }
+}
+
+// ---- the hot pass: row bits of a lane's accumulators into the mask (gf_scrub.hip, gf_checked.hip) ----
+template <int MT>
+__device__ __forceinline__ uint32_t group_bits(const uint32_t (&acc)[MT][4]) {
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) bits |= uint32_t((acc[i][0] | acc[i][1] | acc[i][2] | acc[i][3]) != 0) << i;
+  return bits;
+}
+
+// OR of the wave's row bits into mask word `blk` (wave-uniform): one ballot when the wave is clean,
+// else one per row and a single atomicOr from lane 0. Called with the whole wave converged.
+template <int MT>
+__device__ __forceinline__ void wave_or(uint32_t rowbits, int shift, int* mask, int64_t blk) {
+  if (__builtin_amdgcn_ballot_w64(rowbits != 0) == 0) return;
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+    if (__builtin_amdgcn_ballot_w64(((rowbits >> i) & 1u) != 0) != 0) bits |= 1u << i;
+  if ((threadIdx.x & 63u) == 0) atomicOr(mask + blk, int(bits << shift));
+}
+
+// The mask word of a wave of 16-byte-group lanes whose first lane owns group g0: every group of the
+// wave lies in one 4096-byte span (a workgroup's 256 groups), which block_bytes >= 4096 never
+// splits, and the ragged tail bytes (lanes ngroups .. ngroups + tail - 1) sit right after group
+// ngroups - 1, in the span of group `ngroups`.
+__device__ __forceinline__ int64_t wave_block(int64_t g0, int64_t ngroups, int bshift) {
+  return ((g0 < ngroups ? g0 : ngroups) * 16) >> bshift;
+}
+
+struct Grid {
+  int64_t nblk, ncb;
+  unsigned blocks;
+};
+
+// as gf_gemm.hip's make_grid: at most 2^32 - 1 work-items along x, column blocks padded to a multiple
+// of 8 for the XCD map (short grids unpadded)
+constexpr int64_t kMaxGridBlocks = int64_t(UINT32_MAX) / kBlock;
+inline Grid make_grid(int64_t items, int ntiles) {
+  Grid g{};
+  g.nblk = (items + kBlock - 1) / kBlock;
+  g.ncb = std::min(g.nblk, kMaxGridBlocks / ntiles / 8 * 8);
+  const int64_t ncb8 = g.ncb < 8 ? g.ncb : (g.ncb + 7) / 8 * 8;
+  g.blocks = static_cast<unsigned>(ncb8 * ntiles);
+  return g;
 }
 
 constexpr int kLocSpanShift = 14;  // a workgroup covers min(block_bytes, 16 KiB) columns

@@ -50,33 +50,7 @@ __device__ __forceinline__ uint32_t syn_byte_bits(const DescView& d, int n, int 
   return bits;
 }
 
-template <int MT>
-__device__ __forceinline__ uint32_t group_bits(const uint32_t (&acc)[MT][4]) {
-  uint32_t bits = 0;
-#pragma unroll
-  for (int i = 0; i < MT; ++i) bits |= uint32_t((acc[i][0] | acc[i][1] | acc[i][2] | acc[i][3]) != 0) << i;
-  return bits;
-}
-
-// OR of the wave's row bits into mask word `blk` (wave-uniform): one ballot when the wave is clean,
-// else one per row and a single atomicOr from lane 0. Called with the whole wave converged.
-template <int MT>
-__device__ __forceinline__ void wave_or(uint32_t rowbits, int shift, int* mask, int64_t blk) {
-  if (__builtin_amdgcn_ballot_w64(rowbits != 0) == 0) return;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-    if (__builtin_amdgcn_ballot_w64(((rowbits >> i) & 1u) != 0) != 0) bits |= 1u << i;
-  if ((threadIdx.x & 63u) == 0) atomicOr(mask + blk, int(bits << shift));
-}
-
-// The mask word of a wave of 16-byte-group lanes whose first lane owns group g0: every group of the
-// wave lies in one 4096-byte span (a workgroup's 256 groups), which block_bytes >= 4096 never
-// splits, and the ragged tail bytes (lanes ngroups .. ngroups + tail - 1) sit right after group
-// ngroups - 1, in the span of group `ngroups`.
-__device__ __forceinline__ int64_t wave_block(int64_t g0, int64_t ngroups, int bshift) {
-  return ((g0 < ngroups ? g0 : ngroups) * 16) >> bshift;
-}
+// (group_bits, wave_or and wave_block: scrub_device.h)
 
 // Stripe b = blockIdx.y of a batched launch (gf_gemm.hip's stripe()): its own n row pointers and its
 // own row of ceil(ncols / block_bytes) mask words, both offsets formed in 64 bits. A wave never spans
@@ -358,23 +332,8 @@ __global__ __launch_bounds__(kBlock) void gf_locate_kernel(DescView d, int n, in
 }
 
 // ---- launch -----------------------------------------------------------------------------------
-struct Grid {
-  int64_t nblk, ncb;
-  unsigned blocks;
-};
-
-// as gf_gemm.hip's make_grid: at most 2^32 - 1 work-items along x, column blocks padded to a multiple
-// of 8 for the XCD map (short grids unpadded)
-constexpr int64_t kMaxGridBlocks = int64_t(UINT32_MAX) / kBlock;
-inline Grid make_grid(int64_t items, int ntiles) {
-  Grid g{};
-  g.nblk = (items + kBlock - 1) / kBlock;
-  g.ncb = std::min(g.nblk, kMaxGridBlocks / ntiles / 8 * 8);
-  const int64_t ncb8 = g.ncb < 8 ? g.ncb : (g.ncb + 7) / 8 * 8;
-  g.blocks = static_cast<unsigned>(ncb8 * ntiles);
-  return g;
-}
-
+// (Grid and make_grid: scrub_device.h)
+//
 // The rows-in-flight form is built for the (4, 6) and (10, 14) codes, one tile each; `ident` = the
 // trailing identity columns of H, and with ident == MT the parity rows skip the multiplies.
 // GFRS_TUNE=scrub_rows=0 keeps every launch on the general form, scrub_ident=0 multiplies the

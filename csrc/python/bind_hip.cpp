@@ -175,6 +175,51 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("block_bytes"), py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("max_errors"),
       py::arg("counts"), py::arg("stream") = 0);
   m.def(
+      "checked",
+      [](uint64_t desc, int ns, int e, int r, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask,
+         uint64_t stream) {
+        check(launch_gf_checked(reinterpret_cast<const void*>(desc), ns, e, r, ncols, bytewise, block_bytes,
+                                reinterpret_cast<int32_t*>(mask), as_stream(stream)),
+              "gf_checked");
+      },
+      py::arg("desc"), py::arg("ns"), py::arg("e"), py::arg("r"), py::arg("ncols"), py::arg("bytewise"),
+      py::arg("block_bytes"), py::arg("mask"), py::arg("stream") = 0);
+  m.def(
+      "checked_batched",
+      [](uint64_t desc, int ns, int e, int r, int batch, int64_t ncols, bool bytewise, int64_t block_bytes,
+         uint64_t mask, uint64_t stream) {
+        check(launch_gf_checked_batched(reinterpret_cast<const void*>(desc), ns, e, r, batch, ncols, bytewise,
+                                        block_bytes, reinterpret_cast<int32_t*>(mask), as_stream(stream)),
+              "gf_checked_batched");
+      },
+      py::arg("desc"), py::arg("ns"), py::arg("e"), py::arg("r"), py::arg("batch"), py::arg("ncols"),
+      py::arg("bytewise"), py::arg("block_bytes"), py::arg("mask"), py::arg("stream") = 0);
+  m.def(
+      "checked_fix",
+      [](uint64_t desc, int ns, int e, int r, int64_t ncols, bool bytewise, int64_t block_bytes, uint64_t mask,
+         uint64_t loc, bool locatable, int max_errors, uint64_t counts, uint64_t stream) {
+        check(launch_gf_checked_fix(reinterpret_cast<const void*>(desc), ns, e, r, ncols, bytewise, block_bytes,
+                                    reinterpret_cast<const int32_t*>(mask), reinterpret_cast<const uint8_t*>(loc),
+                                    locatable, max_errors, reinterpret_cast<uint64_t*>(counts), as_stream(stream)),
+              "gf_checked_fix");
+      },
+      py::arg("desc"), py::arg("ns"), py::arg("e"), py::arg("r"), py::arg("ncols"), py::arg("bytewise"),
+      py::arg("block_bytes"), py::arg("mask"), py::arg("loc"), py::arg("locatable"), py::arg("max_errors"),
+      py::arg("counts"), py::arg("stream") = 0);
+  m.def(
+      "checked_fix_batched",
+      [](uint64_t desc, int ns, int e, int r, int batch, int64_t ncols, bool bytewise, int64_t block_bytes,
+         uint64_t mask, uint64_t loc, bool locatable, int max_errors, uint64_t counts, uint64_t stream) {
+        check(launch_gf_checked_fix_batched(reinterpret_cast<const void*>(desc), ns, e, r, batch, ncols, bytewise,
+                                            block_bytes, reinterpret_cast<const int32_t*>(mask),
+                                            reinterpret_cast<const uint8_t*>(loc), locatable, max_errors,
+                                            reinterpret_cast<uint64_t*>(counts), as_stream(stream)),
+              "gf_checked_fix_batched");
+      },
+      py::arg("desc"), py::arg("ns"), py::arg("e"), py::arg("r"), py::arg("batch"), py::arg("ncols"),
+      py::arg("bytewise"), py::arg("block_bytes"), py::arg("mask"), py::arg("loc"), py::arg("locatable"),
+      py::arg("max_errors"), py::arg("counts"), py::arg("stream") = 0);
+  m.def(
       "update",
       [](uint64_t desc, int d, int m_pad, int64_t col0, int64_t ncols, bool pairs, bool store_new, bool bytewise,
          uint64_t stream) {

@@ -440,3 +440,60 @@ def reconstruct_oracle(g: np.ndarray, rows, erased) -> np.ndarray:
     coeff = GF256.matmul(g[erased], GF256.invert(g[survivors]))
     out[erased] = GF256.gemm(coeff, out[survivors])
     return out
+
+
+# ---- checked repair: rebuild erased rows, check and correct the survivors with the surplus parity ----
+def checked_matrix(h: np.ndarray, erased) -> tuple[np.ndarray, list, list, list]:
+    """``(T, X, S, R)`` of a degraded stripe under the check matrix ``h`` (p x n): X the erased ids
+    (sorted, deduplicated; at most p), S the other ids ascending, R the last ``r = p - |X|`` of S (K, the
+    first k of S, are the survivors a rebuild reads) and ``T = inv(h[:, X + R]) . h``, so that
+    ``T[:, X + R] = I_p``. Rows ``0..e-1`` of T rebuild the erased rows from K (they are zero on R),
+    rows ``e..p-1`` check survivor ``R[i]`` against K (they are zero on X). Raises
+    :class:`SingularMatrixError` when K does not determine the data."""
+    h = np.asarray(h, dtype=np.uint8)
+    p, n = h.shape
+    x = sorted(set(int(e) for e in erased))
+    if x and not 0 <= x[0] <= x[-1] < n:
+        raise ValueError(f"erased ids must lie in [0, {n}), got {x}")
+    if len(x) > p:
+        raise ValueError(f"{len(x)} erasures, more than p={p}")
+    s = [i for i in range(n) if i not in x]
+    r = s[n - p:]
+    t = GF256.matmul(GF256.invert(h[:, x + r]), h).astype(np.uint8)
+    return t, x, s, r
+
+
+def reconstruct_checked_oracle(h: np.ndarray, rows, erased, max_errors: int | None = None):
+    """Plain numpy errors-and-erasures repair of an n-row stripe against the check matrix ``h`` (p x n):
+    returns ``(rows_out, fixed_bytes[n], by_weight[3], uncorrectable, bad_columns, T)``; ``rows`` is
+    not modified and its erased rows are never read.
+
+    With :func:`checked_matrix`'s T, X, S, K, R and e = |X|, r = p - e, per byte column c: every erased
+    row ``X[i]`` gets ``w_i = T[i, K] . rows[K, c]`` (what :func:`reconstruct_oracle` writes); the
+    column is bad when ``u = T[e:, S] . rows[S, c] != 0``, and :func:`correct_oracle`'s rule with the
+    r x (n - e) check matrix ``T[e:, S]`` is applied to the survivors (r < 2: uncorrectable). A
+    corrected survivor byte j gets ``^= v`` and each erased row then ``^= v . T[i][j]``, the value
+    rebuilt from the corrected survivors; an uncorrectable column keeps its survivors and ``w``.
+    ``fixed_bytes`` counts survivor bytes by chunk id (erased ids stay 0). ``max_errors``: 1 or 2,
+    default ``min(2, r // 2)`` and at least 1."""
+    h = np.asarray(h, dtype=np.uint8)
+    p, n = h.shape
+    t, x, s, _ = checked_matrix(h, erased)
+    e, r = len(x), p - len(x)
+    k = n - p
+    out = np.array(np.stack([np.asarray(q, dtype=np.uint8) for q in rows]) if not isinstance(rows, np.ndarray)
+                   else rows, dtype=np.uint8)
+    fixed_bytes, by_weight = np.zeros(n, dtype=np.int64), np.zeros(3, dtype=np.int64)
+    if e:
+        out[x] = GF256.gemm(t[:e][:, s[:k]], out[s[:k]])
+    if r == 0:
+        return out, fixed_bytes, by_weight, 0, 0, t
+    if max_errors is None:
+        max_errors = max(1, min(2, r // 2))
+    surv = out[s]
+    fixed, fb, by_weight, uncorrectable, bad_columns = correct_oracle(t[e:][:, s], surv, max_errors)
+    fixed_bytes[s] = fb
+    if e:
+        out[x] ^= GF256.gemm(t[:e][:, s], fixed ^ surv)
+    out[s] = fixed
+    return out, fixed_bytes, by_weight, uncorrectable, bad_columns, t

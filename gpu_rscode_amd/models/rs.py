@@ -20,6 +20,8 @@ import torch
 
 from .. import gf
 from .._native import cpu, hip
+from ..ops.checked import (BatchCheckedRepairPlan, CheckedRepairPlan, check_checked_max_errors, check_erased,
+                           cpu_reconstruct_checked)
 from ..ops.correct import (BatchCorrectPlan, BatchCorrectReport, CorrectPlan, CorrectReport, check_disjoint,
                            check_max_errors, cpu_correct, make_batch_correct_report)
 from ..ops.gemm import Gemm16Plan, GemmPlan
@@ -913,6 +915,105 @@ class ReedSolomon:
         stripe listed twice is refused): ``ValueError`` before anything is written. The limits are
         :meth:`correct`'s."""
         return self._correct("correct_batch", True, stripes, parity, max_errors, block_bytes, stream)
+
+    # ---- checked repair: rebuild the erased chunks, check and correct the survivors ------------------
+    def _reconstruct_checked(self, what: str, batched: bool, stripes, parity, erased, max_errors, block_bytes: int,
+                             stream):
+        """The call behind :meth:`reconstruct_checked` and its batched form: everything is validated
+        before anything is launched or written; then a cached plan on the GPU, or the CPU form stripe
+        by stripe."""
+        if self.field != "gf256":
+            raise NotImplementedError(f"{what} is implemented for field='gf256', not {self.field!r}")
+        if self.p > MAX_LOCATE_P:
+            raise NotImplementedError(f"{what} is implemented for p <= {MAX_LOCATE_P} (p = {self.p})")
+        if batched:
+            batch = StripeBatch(stripes, self.n, parity, self.k)
+            nstripes, ncols, dev = batch.nstripes, batch.ncols, batch.device
+        else:
+            rows, ncols, dev = stripe_rows(stripes, self.n)
+            nstripes = 1
+        block_bytes = check_block_bytes(block_bytes)
+        x = check_erased(erased, self.n, self.p)
+        ns, r = self.n - len(x), self.p - len(x)
+        max_errors = check_checked_max_errors(max_errors, r, ns)
+        nmask = -(-ncols // block_bytes)
+        kernel = dev.type == "cuda" and self.p > 0 and nstripes > 0 and (ncols > 0 or not batched)
+        if kernel:
+            key = (("rchkb", block_bytes, max_errors, tuple(x)) + batch.key if batched
+                   else self._key(("rchk", block_bytes, max_errors, tuple(x)), rows))
+            plan = self._plans.get(key)
+            if plan is not None:
+                return plan.run(stream)
+        survivors = [i for i in range(self.n) if i not in x]
+        if not self.is_recoverable(survivors[: self.k]):
+            raise UnrecoverableError(f"{what}: erased {x} with survivors {survivors[: self.k]}: the survivors do not "
+                                     "determine the data")
+        if batched:
+            check_disjoint(batch.ptrs(), ncols)
+        else:
+            check_disjoint(np.array([[q.data_ptr() for q in rows]], dtype=np.uint64),
+                           np.array([[q.numel() for q in rows]], dtype=np.int64))
+        if kernel:
+            plan = (BatchCheckedRepairPlan(batch, self.H, x, max_errors, block_bytes, check=False) if batched
+                    else CheckedRepairPlan(rows, self.H, x, max_errors, block_bytes, check=False))
+            self._plans[key] = plan
+            return plan.run(stream)
+        mask = torch.zeros((nstripes, nmask), dtype=torch.int32, device=dev)
+        fixed, by_weight = np.zeros((nstripes, self.n), dtype=np.int64), np.zeros((nstripes, 3), dtype=np.int64)
+        unc, bad = np.zeros(nstripes, dtype=np.int64), np.zeros(nstripes, dtype=np.int64)
+        if dev.type != "cuda" and self.p > 0 and nmask:
+            t = gf.checked_matrix(self.H, x)[0]
+            for b in range(nstripes):
+                mask[b], fixed[b], by_weight[b], unc[b], bad[b] = cpu_reconstruct_checked(
+                    t, x, batch.rows(b) if batched else rows, ncols, block_bytes, max_errors, self._cpu_gemm)
+        report = make_batch_correct_report(fixed, by_weight, unc, bad, mask)
+        return report if batched else report.report[0]
+
+    def reconstruct_checked(self, stripe, erased: Sequence[int], max_errors: int | None = None,
+                            block_bytes: int = 65536, stream: torch.cuda.Stream | None = None) -> CorrectReport:
+        """:meth:`reconstruct` that does not trust its survivors: the erased rows are rebuilt from the
+        first k survivors while the other ``r = p - e`` survivors check them, in one pass, and a
+        survivor that is silently wrong is corrected in place with the rebuilt rows following it
+        (errors-and-erasures decoding). ``reconstruct`` alone would write a wrong byte into every
+        rebuilt chunk of such a column, and a later ``scrub`` sees two or more wrong chunks there.
+
+        ``stripe`` as for :meth:`reconstruct`; ``erased``: 0..p ids, sorted and deduplicated here (X).
+        With S the other ids ascending, K the first k of S, R the rest and
+        ``T = inv(H[:, X + R]) . H`` (``gf.checked_matrix``), per byte column: every erased row gets
+        ``T[:e, K] . stripe[K]``, byte for byte what :meth:`reconstruct` writes; the column is bad when
+        ``u = T[e:, S] . stripe[S] != 0``, and :meth:`correct`'s rule with the r x (n - e) check
+        matrix ``T[e:, S]`` is applied to the survivors: a corrected survivor byte j gets ``^= v`` and
+        every erased row ``^= v . T[i][j]``; an uncorrectable column keeps its survivors and the plain
+        rebuild. The erased rows are never read, and nothing but the erased rows and the patched
+        survivor bytes is written. r >= 1 detects, ``r // 2`` wrong survivors per column are
+        corrected (at most 2); r = 1 marks every bad column uncorrectable; r = 0 equals
+        :meth:`reconstruct` and reports clean; e = 0 equals :meth:`correct`.
+
+        Returns a :class:`~gpu_rscode_amd.ops.correct.CorrectReport`: ``bad_columns`` the columns
+        with u != 0, ``fixed_bytes[j]`` the bytes patched in survivor chunk j (erased ids stay 0),
+        ``mask`` bit i set where check row i (survivor ``R[i]``'s re-encoding) is nonzero in that
+        block before correction. On the GPU: the hot launch (n - e rows read, e written), with
+        r >= 1 one launch over the dirty blocks and one sync for the counts; the plan is cached.
+
+        ``max_errors`` defaults to ``min(2, r // 2)`` and at least 1; 2 needs r >= 4 (``ValueError``)
+        and at most 64 survivors (``NotImplementedError``). ``ValueError`` for ids out of range, more
+        than p of them, bad rows, or any two rows overlapping; :class:`UnrecoverableError` when K does
+        not determine the data; ``NotImplementedError`` for another field or p > 16. Every refusal
+        comes before anything is launched and leaves the buffers unchanged."""
+        return self._reconstruct_checked("reconstruct_checked", False, stripe, None, erased, max_errors, block_bytes,
+                                         stream)
+
+    def reconstruct_checked_batch(self, stripes, erased: Sequence[int], parity=None, max_errors: int | None = None,
+                                  block_bytes: int = 65536,
+                                  stream: torch.cuda.Stream | None = None) -> BatchCorrectReport:
+        """:meth:`reconstruct_checked` for B stripes of one shape (the forms of
+        :meth:`syndrome_mask_batch`) under ONE erasure list: a lost node takes the same chunk from
+        every stripe. On the GPU one launch of each kernel (grid.y = stripe) and one sync for the whole
+        batch. Returns a :class:`~gpu_rscode_amd.ops.correct.BatchCorrectReport`, whose ``report[b]``
+        equals what :meth:`reconstruct_checked` returns for stripe b alone. No row may overlap
+        another row of any stripe. The limits are :meth:`reconstruct_checked`'s."""
+        return self._reconstruct_checked("reconstruct_checked_batch", True, stripes, parity, erased, max_errors,
+                                         block_bytes, stream)
 
     # ---- partial-stripe writes ----------------------------------------------------------------
     def _update_rows(self, what: str, changed, parity, first, second):

@@ -1,4 +1,5 @@
-"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, correct, parity update, batched repair."""
+"""Device ops: GF-GEMM, Gauss-Jordan inverse, coding matrices, synthetic data, scrub, correct, parity update, batched repair, checked repair."""
+from .checked import BatchCheckedRepairPlan, CheckedRepairPlan
 from .correct import BatchCorrectPlan, BatchCorrectReport, CorrectPlan, CorrectReport
 from .gemm import Gemm16Plan, GemmPlan, build_desc, desc_layout, gf_gemm, pad_m, perm_tables_from_coeff, tile_for
 from .inverse import PatternDecoder, decode_system16_into_plan, decode_system_into_plan, gf_invert, invert_into_plan
@@ -18,5 +19,6 @@ __all__ = [
     "BatchCorrectPlan", "BatchCorrectReport", "CorrectPlan", "CorrectReport",
     "BatchUpdatePlan", "UpdatePlan",
     "BatchRepairPlan",
+    "BatchCheckedRepairPlan", "CheckedRepairPlan",
     "PickPart", "StripeBatch", "as_rows", "batch_part", "check_parts", "stripe_part", "stripe_rows",
 ]

@@ -277,11 +277,13 @@ def _correct_columns(h: np.ndarray, s: np.ndarray, max_errors: int):
     return weight, js, es
 
 
-def cpu_correct(h: np.ndarray, rows: list[torch.Tensor], ncols: int, block_bytes: int, max_errors: int, cpu_gemm):
+def cpu_correct(h: np.ndarray, rows: list[torch.Tensor], ncols: int, block_bytes: int, max_errors: int, cpu_gemm,
+                on_fix=None):
     """CPU form: syndrome rows slice by slice into p bounded scratch rows (``cpu_gemm(coeff, ins,
     outs)`` is the codec's GEMM, as :func:`~gpu_rscode_amd.ops.scrub.cpu_scrub` takes it), the rule
     in numpy on the bad columns only, the fixes XORed into ``rows`` in place. Returns ``(mask,
-    fixed_bytes, by_weight, uncorrectable, bad_columns)``, the mask that of the stripe as it came."""
+    fixed_bytes, by_weight, uncorrectable, bad_columns)``, the mask that of the stripe as it came.
+    ``on_fix(j, cols, values)`` is called for the bytes ``cols`` of row j that got ``^= values``."""
     h = np.asarray(h, dtype=np.uint8)
     p, n = h.shape
     block_bytes = check_block_bytes(block_bytes)
@@ -317,6 +319,8 @@ def cpu_correct(h: np.ndarray, rows: list[torch.Tensor], ncols: int, block_bytes
                 at = sel[js[w - 1, sel] == j]
                 host[j][c0 + cols[at]] ^= es[w - 1, at]
                 fixed_bytes[j] += int(at.size)
+                if on_fix is not None:
+                    on_fix(int(j), c0 + cols[at], es[w - 1, at])
             by_weight[w] += int((weight == w).sum())
         uncorrectable += int((weight == 0).sum())
     return torch.from_numpy(bits.view(np.int32)), fixed_bytes, by_weight, uncorrectable, bad_columns
