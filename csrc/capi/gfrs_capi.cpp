@@ -400,6 +400,7 @@ int gfrs_plan_create(gfrs_plan** plan, int device, int k, int m, const uint8_t* 
                      void* const* out, void* const* copy, int64_t ncols, int engine) {
   return guarded([&] {
     need(plan && coeff && in && out, "plan_create: plan, coeff, in and out are required");
+    need(k >= 1 && k <= 256 && m >= 1 && m <= 256, "plan_create: 1 <= k, m <= 256");  // before k, m size a read
     auto p = std::make_unique<gfrs_plan>();
     std::vector<uint64_t> cp;
     if (copy) cp = addrs(const_cast<const void* const*>(copy), k);

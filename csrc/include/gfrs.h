@@ -58,7 +58,12 @@ int gfrs_decode_matrix(const uint8_t* e, int k, int p, const int* survivors, uin
 typedef struct gfrs_plan gfrs_plan;
 /* in: k device rows, out: m device rows, copy: NULL or k device rows (input j is also copied to
  * copy[j] in the same pass when copy[j] != NULL: the fused survivor copy of a decode); coeff: m x k
- * host matrix. Engine AUTO picks the FP4 matrix-core kernel for wide stripes (k >= 64, m >= 16). */
+ * host matrix. Engine AUTO picks the FP4 matrix-core kernel for wide stripes (k >= 64, m >= 16).
+ * Rows may sit at any spacing and order. A row that is not 16-byte aligned puts the plan on the
+ * v_perm kernel's byte form: AUTO then reports GFRS_ENGINE_VALU, and GFRS_ENGINE_MFMA is
+ * GFRS_EINVAL. A row with no copy destination is not written. ncols == 0 succeeds, in create and
+ * in run, and writes nothing. Argument errors are GFRS_EINVAL before any HIP call; *plan is then
+ * left as it was. set_coeff replaces the matrix for every column of the next run, on both engines. */
 int gfrs_plan_create(gfrs_plan** plan, int device, int k, int m, const uint8_t* coeff, const void* const* in,
                      void* const* out, void* const* copy, int64_t ncols, int engine);
 int gfrs_plan_set_coeff(gfrs_plan* plan, const uint8_t* coeff); /* synchronous */
@@ -93,7 +98,8 @@ void gfrs_plan16_destroy(gfrs_plan16* plan);
  * place. store_new (pair form only): old_or_delta[t] is also overwritten with new_rows[t] in the
  * same pass, so a write into a stripe is one call. 1 <= d <= 256 (more than 8 run as passes of 8),
  * 1 <= p <= 255. run covers byte columns [col0, col0 + ncols) of every row, asynchronously on
- * stream; there no parity row may overlap another row, nor a new row an old one (GFRS_EINVAL). */
+ * stream; there no parity row may overlap another row, nor a new row an old one (GFRS_EINVAL, nothing
+ * written; rows exactly ncols bytes apart do not overlap). ncols == 0 succeeds and writes nothing. */
 typedef struct gfrs_update gfrs_update;
 int gfrs_update_create(gfrs_update** upd, int device, int d, int p, const uint8_t* coeff, void* const* old_or_delta,
                        const void* const* new_rows, void* const* parity, int store_new);
@@ -105,7 +111,10 @@ void gfrs_update_destroy(gfrs_update* upd);
  * 16-byte aligned; e: p x k host encoding matrix; erased: natives lost per pattern (1..min(k, p)).
  * gfrs_decoder_rows() is a device int32[k] buffer for the survivor ids (write it with a kernel, a
  * copy or an RCCL broadcast); solve checks the pattern and builds the plan on the device; run
- * rebuilds the erased natives into out and copies the surviving natives in the same pass. */
+ * rebuilds the erased natives into out and copies the surviving natives in the same pass. It never
+ * writes the chunk rows. A survivor list with a repeated id, an id outside [0, n) or another number
+ * of missing natives than `erased` is status 2, an unrecoverable one status 1: after such a solve
+ * run returns GFRS_OK and stores nothing, and the next good pattern solved decodes as usual. */
 typedef struct gfrs_decoder gfrs_decoder;
 int gfrs_decoder_create(gfrs_decoder** dec, int device, int k, int p, const uint8_t* e, void* const* chunks,
                         void* const* out, int64_t ncols, int erased, int engine);
@@ -118,6 +127,10 @@ int gfrs_decoder_engine(const gfrs_decoder* dec); /* GFRS_ENGINE_VALU or GFRS_EN
 void gfrs_decoder_destroy(gfrs_decoder* dec);
 
 /* ---- host rows through the streaming pipeline (pinned rows give async DMA) ------------------- */
+/* Rows may be pinned or pageable, at any alignment and spacing; only columns [0, ncols) of the out
+ * rows are written. devices NULL / ndev 0: device 0; the columns are sharded over the list at
+ * multiples of 4 KiB (a short range leaves the leading shards empty). streams <= 0: 2; slice_bytes
+ * <= 0: the default slice. ncols == 0 succeeds and writes nothing. */
 int gfrs_gemm_host(const int* devices, int ndev, int k, int m, const uint8_t* coeff, const uint8_t* const* in,
                    uint8_t* const* out, int64_t ncols, int streams, int64_t slice_bytes);
 

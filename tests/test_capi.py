@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import capi_cases as cc
 from gpu_rscode_amd import _build, gf
 from gpu_rscode_amd.models import ReedSolomon
 
@@ -82,6 +83,85 @@ def test_bad_arguments_are_reported_not_crashed(lib):
     assert b"no file" in lib.gfrs_last_error()
     plan = ctypes.c_void_p()
     assert lib.gfrs_plan_create(ctypes.byref(plan), 0, 0, 4, None, None, None, None, 0, 0) == -1
+
+
+# ---- refusals that come before the first HIP call: no GPU needed, the row addresses are host-side
+# sentinels that nothing dereferences ---------------------------------------------------------------
+def _sentinels(n, first=0x7F0000000000, step=0x1000):
+    return cc.ptr_array([first + i * step for i in range(n)])
+
+
+def _refused(c, rc):
+    assert rc == cc.EINVAL, (rc, cc.err(c))
+    assert cc.err(c), "GFRS_EINVAL without a message"
+
+
+@pytest.mark.parametrize("what", ["k=0", "k=257", "k=-1", "m=0", "m=257", "ncols<0", "engine=3", "plan=NULL", "coeff=NULL",
+                                  "in=NULL", "out=NULL"])
+def test_plan_create_refusals(what):
+    c = cc.load()
+    k, m, ncols, engine = 10, 4, 4096, cc.AUTO
+    if what[1] == "=" and what[2:].lstrip("-").isdigit():
+        k, m = (int(what[2:]), m) if what[0] == "k" else (k, int(what[2:]))
+    plan = ctypes.c_void_p()
+    args = {"plan": ctypes.byref(plan), "coeff": bytes(257 * 257), "in": _sentinels(257), "out": _sentinels(257, 0x7F1000000000)}
+    if what.endswith("=NULL"):
+        args[what[:-5]] = None
+    rc = c.gfrs_plan_create(args["plan"], 0, k, m, args["coeff"], args["in"], args["out"], _sentinels(257, 0x7F2000000000),
+                            -1 if what == "ncols<0" else ncols, 3 if what == "engine=3" else engine)
+    _refused(c, rc)
+    assert not plan.value
+
+
+@pytest.mark.parametrize("what", ["odd ncols", "odd input row", "odd output row", "odd copy row"])
+def test_plan16_create_refusals(what):
+    c = cc.load()
+    k, m = 4, 2
+    coeff = np.ones((m, k), dtype=np.uint16)
+    ins, outs, copies = ([0x7F0000000000 + 0x1000 * (8 * t + i) for i in range(k)] for t in range(3))
+    for name, rows in (("input", ins), ("output", outs), ("copy", copies)):
+        if name in what:
+            rows[1] += 1
+    plan = ctypes.c_void_p()
+    rc = c.gfrs_plan16_create(ctypes.byref(plan), 0, k, m, coeff.ctypes.data, cc.ptr_array(ins), cc.ptr_array(outs[:m]),
+                              cc.ptr_array(copies), 4097 if what == "odd ncols" else 4096, cc.VALU)
+    _refused(c, rc)
+    assert not plan.value
+
+
+@pytest.mark.parametrize("what", ["erased=0", "erased=min(k,p)+1", "misaligned chunk row", "NULL chunk row",
+                                  "misaligned output row", "NULL output row"])
+def test_decoder_create_refusals(what):
+    c = cc.load()
+    k, p = 10, 4
+    e = ReedSolomon(k, k + p).E
+    chunks = [0x7F0000000000 + 0x1000 * i for i in range(k + p)]
+    outs = [0x7F1000000000 + 0x1000 * i for i in range(k)]
+    rows = chunks if "chunk" in what else outs
+    if "misaligned" in what:
+        rows[-1] += 8
+    if "NULL" in what:
+        rows[-1] = 0
+    erased = {"erased=0": 0, "erased=min(k,p)+1": min(k, p) + 1}.get(what, 2)
+    dec = ctypes.c_void_p()
+    rc = c.gfrs_decoder_create(ctypes.byref(dec), 0, k, p, cc.coeff_bytes(e), cc.ptr_array(chunks), cc.ptr_array(outs), 4096,
+                               erased, cc.AUTO)
+    _refused(c, rc)
+    assert not dec.value
+
+
+@pytest.mark.parametrize("what", ["old", "new", "parity"])
+def test_update_create_refuses_a_null_row(what):
+    c = cc.load()
+    d, p = 3, 2
+    rows = {"old": [0x7F0000000000 + 0x1000 * i for i in range(d)], "new": [0x7F1000000000 + 0x1000 * i for i in range(d)],
+            "parity": [0x7F2000000000 + 0x1000 * i for i in range(p)]}
+    rows[what][1] = 0
+    u = ctypes.c_void_p()
+    rc = c.gfrs_update_create(ctypes.byref(u), 0, d, p, bytes(range(1, d * p + 1)), cc.ptr_array(rows["old"]),
+                              cc.ptr_array(rows["new"]), cc.ptr_array(rows["parity"]), 0)
+    _refused(c, rc)
+    assert "null row" in cc.err(c) and not u.value
 
 
 @pytest.mark.gpu
