@@ -190,6 +190,23 @@ hipError_t launch_gf_update_batched(const void* desc, int k, int d, int m_pad, i
 hipError_t launch_gf_repair_batched(const void* desc, int k, int m_pad, int batch, int npat, int64_t ncols,
                                     bool force_bytewise, hipStream_t stream);
 
+// ---- device-built repair coefficients (csrc/kernels/gf_repair_solve.hip) ------------------------
+// Solves `npat` erasure patterns of one (n, k) GF(2^8) code in one launch, one workgroup each
+// (grid.x = pattern): g = G (n x k, [I; E]) on the device, surv int32 [npat][k] the survivors of each
+// pattern in the order of its coefficient columns, erased int32 [npat][m_pad] the rows to rewrite,
+// padded with -1. Pattern q's rows G[erased_q] . inv(G[surv_q]) go to coeff + q * m_pad * k (m_pad x k
+// bytes, zero rows where erased is -1) and, as v_perm records tab[q][j][i], to the q-th (k, m_pad)
+// table block at `tab`: the table block of a repair_batch_layout descriptor, or with npat = 1 that of
+// a desc_layout one. Either may be null. status[q] = 0 built, 1 singular, 2 invalid lists (an id
+// outside [0, n), a survivor or an erased id listed twice, an erased id among the survivors); a
+// pattern whose status is not 0 writes neither coefficients nor table words. hipErrorInvalidValue,
+// and nothing launched, for npat < 0, k outside [1, n], n > 256, m_pad outside [1, 256], a null g,
+// surv, erased or status, or a system that does not fit the LDS (repair_solve_lds_bytes above 64 KiB:
+// none with n <= 256); npat == 0 succeeds without a launch and reads no pointer.
+int64_t repair_solve_lds_bytes(int n, int k, int m_pad);  // -1: a shape the launcher refuses
+hipError_t launch_gf_repair_solve(const uint8_t* g, int n, int k, const int* surv, const int* erased, int npat,
+                                  int m_pad, uint8_t* coeff, void* tab, int* status, hipStream_t stream);
+
 // ---- Gauss-Jordan inverse (csrc/kernels/gf_invert.hip)---------------------------------------
 // Inverts `batch` n x n matrices (row-major, contiguous) with row pivoting, one workgroup each,
 // [A|I] resident in LDS. status[b] = 0 ok, 1 singular. n <= 256.

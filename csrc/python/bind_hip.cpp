@@ -249,6 +249,20 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("ncols"),
       py::arg("bytewise"), py::arg("stream") = 0);
   m.def(
+      "repair_solve",
+      [](uint64_t g, int n, int k, uint64_t surv, uint64_t erased, int npat, int m_pad, uint64_t coeff, uint64_t tab,
+         uint64_t status, uint64_t stream) {
+        check(launch_gf_repair_solve(reinterpret_cast<const uint8_t*>(g), n, k, reinterpret_cast<const int*>(surv),
+                                     reinterpret_cast<const int*>(erased), npat, m_pad,
+                                     reinterpret_cast<uint8_t*>(coeff), reinterpret_cast<void*>(tab),
+                                     reinterpret_cast<int*>(status), as_stream(stream)),
+              "gf_repair_solve");
+      },
+      py::arg("g"), py::arg("n"), py::arg("k"), py::arg("surv"), py::arg("erased"), py::arg("npat"), py::arg("m_pad"),
+      py::arg("coeff") = 0, py::arg("tab") = 0, py::arg("status") = 0, py::arg("stream") = 0);
+  m.def("repair_solve_lds_bytes", &repair_solve_lds_bytes,
+        "LDS bytes of one workgroup of the repair solve (-1: a shape the launcher refuses)");
+  m.def(
       "invert",
       [](uint64_t a, uint64_t a_inv, int n, int batch, uint64_t status, uint64_t desc, uint64_t sel_rows, int mm,
          int m_pad, uint64_t stream) {

@@ -442,6 +442,50 @@ def reconstruct_oracle(g: np.ndarray, rows, erased) -> np.ndarray:
     return out
 
 
+def repair_coeff_oracle(g: np.ndarray, survivors, erased) -> np.ndarray:
+    """Plain numpy form of the route ``csrc/kernels/gf_repair_solve.hip`` takes to the repair
+    coefficients ``G[erased] . inv(G[survivors])`` (e x k over GF(2^8), columns in the order of
+    ``survivors``, rows in the order of ``erased``) of a systematic generator ``g = [I; E]``, without
+    the k x k inverse. With Mn the natives that are no survivors and P the parity survivors (as many),
+    the systematic solve ``X = inv(G[P, Mn]) . B'`` gives the rows of the natives in Mn, where
+    ``B'[r][c]`` is ``G[P_r][survivors_c]`` for a native survivor and ``[survivors_c == P_r]`` for a
+    parity one; an erased parity row x is its base row (``G[x][survivors_c]`` for a native survivor,
+    0 for a parity one) plus ``G[x, Mn] . X``. Raises :class:`SingularMatrixError` where
+    ``G[P, Mn]`` is singular (exactly where ``G[survivors]`` is) and ``ValueError`` for lists that are
+    not k distinct survivors in ``[0, n)`` and erased ids in ``[0, n)`` that are no survivors."""
+    g = np.asarray(g, dtype=np.uint8)
+    n, k = g.shape
+    sv = [int(s) for s in survivors]
+    er = [int(x) for x in erased]
+    if len(sv) != k or len(set(sv)) != k or min(sv) < 0 or max(sv) >= n:
+        raise ValueError(f"need {k} distinct survivor ids in [0, {n})")
+    if er and (min(er) < 0 or max(er) >= n or set(er) & set(sv)):
+        raise ValueError(f"erased ids must lie in [0, {n}) and be no survivors")
+    native = np.array([s < k for s in sv], dtype=bool)
+    mn = [i for i in range(k) if i not in set(sv)]
+    par = [s for s in sv if s >= k]
+    sv_nat = [s if s < k else 0 for s in sv]  # (a parity survivor's column index is never used)
+
+    def base(ids, identity: bool) -> np.ndarray:
+        b = np.where(native[None, :], g[np.ix_(ids, sv_nat)], 0).astype(np.uint8)
+        if identity:
+            b |= (np.array(ids)[:, None] == np.array(sv)[None, :]).astype(np.uint8)
+        return b
+
+    x = np.zeros((0, k), dtype=np.uint8)
+    if mn:  # (|P| == |Mn|: the k survivors are distinct)
+        x = GF256.matmul(GF256.invert(g[np.ix_(par, mn)]), base(par, True))
+    out = np.zeros((len(er), k), dtype=np.uint8)
+    for i, e in enumerate(er):
+        if e < k:
+            out[i] = x[mn.index(e)]
+        else:
+            out[i] = base([e], False)[0]
+            if mn:
+                out[i] ^= GF256.matmul(g[[e]][:, mn], x)[0]
+    return out
+
+
 # ---- checked repair: rebuild erased rows, check and correct the survivors with the surplus parity ----
 def checked_matrix(h: np.ndarray, erased) -> tuple[np.ndarray, list, list, list]:
     """``(T, X, S, R)`` of a degraded stripe under the check matrix ``h`` (p x n): X the erased ids

@@ -506,12 +506,9 @@ class ReedSolomon:
                 plan.rows_dev = torch.tensor(rows, dtype=torch.int32, device=dev)
                 plan.erased_dev = torch.tensor(erased, dtype=torch.int32, device=dev)
                 plan.status = torch.zeros(1, dtype=torch.int32, device=dev)
-            g_dev = self._g_dev.get((dev, id(self.G)))
-            if g_dev is None:
-                self._g_dev.clear()
-                g_dev = self._g_dev[(dev, id(self.G))] = torch.from_numpy(np.ascontiguousarray(self.G)).to(dev)
             # systematic decode solved on device: e x (e+k) Gauss-Jordan, tables written in place
-            decode_system_into_plan(g_dev, plan.rows_dev, plan.erased_dev, plan, status=plan.status, stream=stream)
+            decode_system_into_plan(self._g_device(dev), plan.rows_dev, plan.erased_dev, plan, status=plan.status,
+                                    stream=stream)
             self.last_status = plan.status
         elif device_invert and self.wide and decode16_device_supported(self.n, self.k, len(erased)):
             plan = self._plans.get(key)
@@ -537,10 +534,62 @@ class ReedSolomon:
         plan.run(stream)
         return out
 
+    def _g_device(self, dev: torch.device) -> torch.Tensor:
+        """G on ``dev`` for the device solves (GF(2^8)), uploaded once per generator."""
+        g_dev = self._g_dev.get((dev, id(self.G)))
+        if g_dev is None:
+            self._g_dev.clear()
+            g_dev = self._g_dev[(dev, id(self.G))] = torch.from_numpy(np.ascontiguousarray(self.G)).to(dev)
+        return g_dev
+
+    def _reconstruct_solved(self, ins, outs, survivors, erased, stream) -> None:
+        """:meth:`reconstruct` with ``device_solve=True`` on the GPU: the pattern's coefficients come
+        from ``gf_repair_solve.hip`` as v_perm tables in the plan's descriptor and, on the matrix-core
+        engine, as the bit-matrix built from the raw coefficients. The status is read before the GEMM."""
+        from ..ops.repair import solve_patterns
+
+        if self.field != "gf256":
+            raise NotImplementedError(f"device_solve is implemented for field='gf256', not {self.field!r}")
+        if len(survivors) != self.k or len(set(survivors)) != self.k or min(survivors) < 0 or max(survivors) >= self.n:
+            raise ValueError(f"need {self.k} distinct chunk ids in [0, {self.n})")
+        if min(erased) < 0 or max(erased) >= self.n or set(erased) & set(survivors):
+            raise ValueError(f"erased ids must lie in [0, {self.n}) and be no survivors")
+        key = self._key(("repd", tuple(survivors), tuple(erased)), ins, outs)
+        plan = self._plans.get(key)
+        if plan is None:
+            dev = ins[0].device
+            plan = GemmPlan(ins, outs, device_tables=True, hold_buffers=False)
+            ids = torch.full((self.k + plan.m_pad,), -1, dtype=torch.int32)
+            ids[: self.k] = torch.tensor(survivors, dtype=torch.int32)
+            ids[self.k: self.k + len(erased)] = torch.tensor(erased, dtype=torch.int32)
+            ids = ids.to(dev)
+            coeff = torch.empty((plan.m_pad, self.k), dtype=torch.uint8, device=dev)
+            status = solve_patterns(self._g_device(dev), ids[: self.k].view(1, -1), ids[self.k:].view(1, -1), plan.m_pad,
+                                    coeff_out=coeff, tables_out=plan.desc[plan.layout.tab_off:])
+            status = int(status.item())  # the one sync, before anything is written
+            if status == 1:
+                raise UnrecoverableError(f"reconstruct: erased {erased} cannot be repaired from survivors "
+                                         f"{survivors}: singular decode system")
+            if status:
+                raise RuntimeError(f"the repair solve refused erased {erased} with survivors {survivors}")
+            if plan.engine == "mfma":
+                plan.set_device_coeff(coeff)
+            plan._mark_ready()
+            self._plans[key] = plan
+        plan.run(stream)
+
     def reconstruct(self, stripe, erased: Sequence[int], survivors: Sequence[int] | None = None,
-                    stream: torch.cuda.Stream | None = None):
+                    stream: torch.cuda.Stream | None = None, device_solve: bool = False):
         """In-place repair of an n-row stripe: rewrite rows ``erased`` (natives and/or parity) from k
-        surviving rows. One GEMM: rows = G[erased] . inv(G[survivors]) . survivors."""
+        surviving rows. One GEMM: rows = G[erased] . inv(G[survivors]) . survivors.
+
+        ``device_solve=True`` (CUDA tensors, ``field="gf256"``) solves the pattern on the GPU
+        (``csrc/kernels/gf_repair_solve.hip``) instead of inverting ``G[survivors]`` on the host; the
+        GEMM runs on the engine the default call picks, from device-written tables. The first call of a
+        pattern reads one status word back before the GEMM is launched (a singular pattern raises
+        :class:`UnrecoverableError` with the stripe unchanged); a repeat call is the cached launch.
+        ``gf16`` / ``gf65536`` on the GPU raise ``NotImplementedError`` with the flag set; CPU tensors
+        ignore it and take the CPU path."""
         rows_all = as_rows(stripe)
         if len(rows_all) != self.n:
             raise ValueError(f"stripe must have n={self.n} rows")
@@ -551,6 +600,10 @@ class ReedSolomon:
         if len(survivors) < self.k:
             raise UnrecoverableError(f"only {len(survivors)} survivors, need k={self.k}")
         if not erased:
+            return stripe
+        if device_solve and rows_all[0].device.type == "cuda":
+            self._reconstruct_solved([rows_all[s] for s in survivors if 0 <= s < self.n],
+                                     [rows_all[e] for e in erased if 0 <= e < self.n], survivors, erased, stream)
             return stripe
         dm = self.decode_matrix(survivors)
         coeff = self.gf.matmul(self.G[erased], dm).astype(self.G.dtype)
@@ -596,11 +649,12 @@ class ReedSolomon:
             raise ValueError(f"{what}: expected ids, B id sequences or an integer [B, e] array, got shape {tuple(a.shape)}")
         return np.ascontiguousarray(a, dtype=np.int64)
 
-    def _erased_patterns(self, a: np.ndarray, nstripes: int):
+    def _erased_patterns(self, a: np.ndarray, nstripes: int, solve: bool = True):
         """The validated patterns of a batch from :meth:`_erased_raw`'s array: (``pat`` int64 ``[B]``, -1
         for a stripe with nothing erased; the distinct patterns as ``(survivors, erased)`` id tuples,
         in the order their first stripes come). Ids sorted and deduplicated per stripe, the
-        survivors the first k ids not erased, every pattern solved once (``self._dm`` caches)."""
+        survivors the first k ids not erased, every pattern solved once (``self._dm`` caches) unless
+        ``solve`` is False (the caller solves them on the device)."""
         what = "reconstruct_batch: erased"
         shared = a.ndim == 1
         if shared:
@@ -635,14 +689,16 @@ class ReedSolomon:
         for er, b in first.items():
             sv = tuple(i for i in range(n) if i not in er)[: self.k]
             try:
-                self.decode_matrix(sv)
+                if solve:
+                    self.decode_matrix(sv)
             except UnrecoverableError as e:
                 raise UnrecoverableError(f"reconstruct_batch: {'the pattern' if shared else f'stripe {b}'} cannot be "
                                          f"repaired: erased {list(er)} with survivors {list(sv)}: {e}") from None
             patterns.append((sv, er))
         return (np.broadcast_to(pat, (nstripes,)) if shared else pat), patterns
 
-    def reconstruct_batch(self, stripes, erased, parity=None, stream: torch.cuda.Stream | None = None):
+    def reconstruct_batch(self, stripes, erased, parity=None, stream: torch.cuda.Stream | None = None,
+                          device_solve: bool = False):
         """:meth:`reconstruct` for B stripes of one shape in ONE launch (grid.y = stripe), each stripe
         with erasures OF ITS OWN: after real failures objects placed over different node sets have
         lost different chunks, and one by one the repairs of small objects are launch-bound.
@@ -660,18 +716,32 @@ class ReedSolomon:
         or a row to rewrite that overlaps any other row the batch uses (so also for a stripe listed
         twice); :class:`UnrecoverableError` for a stripe with more than p erasures or a singular
         pattern, naming the first such stripe. CPU tensors, and ``gf65536`` on the GPU, loop over the
-        stripes with :meth:`reconstruct`. Returns ``stripes``."""
+        stripes with :meth:`reconstruct`. Returns ``stripes``.
+
+        ``device_solve=True`` (CUDA tensors, ``field="gf256"``) builds the coefficient tables on the
+        GPU: the ids are validated and de-duplicated into distinct patterns on the host as ever, but no
+        pattern is solved there. The descriptor goes up with empty table blocks, one launch of
+        ``csrc/kernels/gf_repair_solve.hip`` (a workgroup per distinct pattern) fills them in place and
+        the statuses are read back once, the only host sync and only on the first call: the plan is
+        cached under a key of its own, so a repeat call is dict lookups and the repair launch, with no
+        second solve. The bytes written are those of the default call. A singular pattern raises
+        :class:`UnrecoverableError` naming the first stripe that uses it, after the solve and before the
+        repair kernel: no stripe is touched. ``gf16`` and ``gf65536`` on the GPU raise
+        ``NotImplementedError`` with the flag set; CPU tensors ignore it and take the CPU path."""
         from ..ops.repair import BatchRepairPlan, check_repair_overlap, repair_rows
 
         batch = StripeBatch(stripes, self.n, parity, self.k)
+        solved = bool(device_solve) and batch.device.type == "cuda"
+        if solved and self.field != "gf256":
+            raise NotImplementedError(f"device_solve is implemented for field='gf256', not {self.field!r}")
         raw = self._erased_raw(erased, self.n)
         kernel = batch.device.type == "cuda" and not self.wide
-        key = ("repb", batch.key, raw.shape, raw.tobytes()) if kernel else None
+        key = ("repbd" if solved else "repb", batch.key, raw.shape, raw.tobytes()) if kernel else None
         plan = self._plans.get(key) if kernel else None
         if plan is not None:  # a repeat call on the same buffers and patterns: dict lookups and the launch
             plan.run(stream)
             return stripes
-        pat, patterns = self._erased_patterns(raw, batch.nstripes)
+        pat, patterns = self._erased_patterns(raw, batch.nstripes, solve=not solved)
         keep = pat >= 0
         if not keep.any() or batch.ncols == 0:
             return stripes
@@ -680,6 +750,23 @@ class ReedSolomon:
         m_pad = max(len(er) for _, er in patterns)
         check_repair_overlap(*repair_rows(batch.ptrs()[keep], pat[keep], [(sv, er, None) for sv, er in patterns], m_pad),
                              batch.ncols)
+        if solved:
+            plan = BatchRepairPlan(batch, pat, [(sv, er, None) for sv, er in patterns], check=False,
+                                   g_dev=self._g_device(batch.device))
+            bad = np.nonzero(plan.status)[0]
+            if bad.size:
+                q = int(bad[0])  # (patterns come in the order of their first stripes)
+                sv, er = patterns[q]
+                if plan.status[q] != 1:
+                    raise RuntimeError(f"the repair solve refused erased {list(er)} with survivors {list(sv)}")
+                who = "the pattern" if raw.ndim == 1 else f"stripe {int(np.nonzero(pat == q)[0][0])}"
+                err = UnrecoverableError(f"reconstruct_batch: {who} cannot be repaired: erased {list(er)} with "
+                                         f"survivors {list(sv)}: singular decode system")
+                err.stripes = np.nonzero(np.isin(pat, bad))[0].tolist()  # every stripe with such a pattern
+                raise err
+            self._plans[key] = plan
+            plan.run(stream)
+            return stripes
         if kernel:
             full = []
             for sv, er in patterns:
@@ -800,7 +887,8 @@ class ReedSolomon:
         :meth:`scrub` returns for stripe b alone. p > 16 raises ``NotImplementedError``."""
         return self._scrub("scrub_batch", True, stripes, parity, block_bytes, stream, True)
 
-    def heal_batch(self, stripes, parity=None, report: BatchScrubReport | None = None) -> BatchScrubReport:
+    def heal_batch(self, stripes, parity=None, report: BatchScrubReport | None = None,
+                   device_solve: bool = False) -> BatchScrubReport:
         """Repair the dirty stripes of a batch in place, each from its own redundancy. Scrubs if no
         ``report`` is given. A dirty stripe that passes :meth:`heal`'s rule (no unlocated column, 1..p
         suspects) is rewritten as ``reconstruct(stripe_b, erased=suspects_b)`` would, all such stripes
@@ -808,12 +896,15 @@ class ReedSolomon:
         decode system, is left byte for byte as it was and listed in ``unhealed``. Nothing
         is raised for it: one bad object does not stop the batch. If anything was rewritten the whole
         batch is scrubbed once more and that second report is returned, else the first; either has
-        ``unhealed`` filled in."""
+        ``unhealed`` filled in. ``device_solve`` is passed to :meth:`reconstruct_batch`: on the GPU the
+        suspects' patterns are then solved there, the singular ones come back from that solve, and the
+        others are repaired by a second call (the first wrote nothing); CPU tensors ignore it."""
         if self.field != "gf256":
             raise NotImplementedError(f"heal_batch is implemented for field='gf256', not {self.field!r}")
         if report is None:
             report = self.scrub_batch(stripes, parity)
         batch = StripeBatch(stripes, self.n, parity, self.k)
+        solved = bool(device_solve) and batch.device.type == "cuda"
         unhealed = []
         erased = np.full((batch.nstripes, self.p), -1, dtype=np.int64)
         for b in report.dirty:
@@ -822,11 +913,22 @@ class ReedSolomon:
                 unhealed.append(b)
                 continue
             sus = sorted(set(int(e) for e in rep.suspects))
-            if not self.is_recoverable([i for i in range(self.n) if i not in sus][: self.k]):
+            # (with the device solve the singular patterns are found by that solve, below)
+            if not solved and not self.is_recoverable([i for i in range(self.n) if i not in sus][: self.k]):
                 unhealed.append(b)  # (a singular decode system: nothing is written)
                 continue
             erased[b, : len(sus)] = sus
-        if (erased >= 0).any():
+        if solved and (erased >= 0).any():
+            try:
+                self.reconstruct_batch(stripes, erased, parity, device_solve=True)
+            except UnrecoverableError as e:  # raised before a byte is written, with every such stripe
+                erased[e.stripes] = -1
+                unhealed = sorted(unhealed + e.stripes)
+                if (erased >= 0).any():
+                    self.reconstruct_batch(stripes, erased, parity, device_solve=True)
+            if (erased >= 0).any():
+                report = self.scrub_batch(stripes, parity)
+        elif (erased >= 0).any():
             self.reconstruct_batch(stripes, erased, parity)
             report = self.scrub_batch(stripes, parity)
         report.unhealed = unhealed

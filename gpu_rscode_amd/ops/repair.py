@@ -64,6 +64,66 @@ def repair_tables(patterns, k: int, m_pad: int) -> np.ndarray:
     return tab
 
 
+def pattern_ids(patterns, m_pad: int) -> tuple[np.ndarray, np.ndarray]:
+    """The id arrays of ``patterns[q] = (survivors, erased, ...)``: int32 ``[npat, k]`` survivors and
+    int32 ``[npat, m_pad]`` erased ids padded with -1 (what :func:`solve_patterns` takes)."""
+    surv = np.array([list(p[0]) for p in patterns], dtype=np.int32).reshape(len(patterns), -1)
+    er = np.full((len(patterns), m_pad), -1, dtype=np.int32)
+    for q, p in enumerate(patterns):
+        er[q, : len(p[1])] = list(p[1])
+    return surv, er
+
+
+def solve_patterns(g_dev: torch.Tensor, surv: torch.Tensor, erased: torch.Tensor, m_pad: int, *,
+                   coeff_out: torch.Tensor | None = None, tables_out: torch.Tensor | None = None,
+                   stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """Solve erasure patterns on the device (``csrc/kernels/gf_repair_solve.hip``), one workgroup per
+    pattern in one launch, no host work per pattern.
+
+    ``g_dev``: the ``(n, k)`` uint8 generator ``[I; E]`` on the GPU. ``surv``: int32 ``[npat, k]`` on
+    the same device, each pattern's survivors in the order of its coefficient columns. ``erased``:
+    int32 ``[npat, m_pad]``, the rows to rewrite, padded with -1. ``coeff_out``: uint8, at least
+    ``npat * m_pad * k`` elements, contiguous: pattern q's ``m_pad x k`` block of
+    ``G[erased_q] . inv(G[surv_q])``, zero rows at the padding. ``tables_out``: a contiguous device
+    tensor whose first ``npat * k * m_pad * 32`` bytes are the ``(npat, k, m_pad, 8)`` uint32 v_perm
+    records: the table block of a ``repair_batch_layout`` descriptor (or of a
+    :class:`~gpu_rscode_amd.ops.gemm.GemmPlan` descriptor, one pattern). Either may be None. Returns
+    the int32 ``[npat]`` device status: 0 built, 1 singular, 2 invalid lists; a pattern whose status
+    is not 0 leaves its blocks untouched. Asynchronous on ``stream`` (default: the current one); a
+    shape whose system does not fit one workgroup's LDS raises ``NotImplementedError``."""
+    if g_dev.dtype != torch.uint8 or g_dev.dim() != 2 or not g_dev.is_cuda or not g_dev.is_contiguous():
+        raise ValueError("g_dev must be a contiguous 2-D uint8 tensor on a GPU")
+    n, k = (int(v) for v in g_dev.shape)
+    dev = g_dev.device
+    for name, t, width in (("surv", surv, k), ("erased", erased, m_pad)):
+        if t.dtype != torch.int32 or t.device != dev or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int32 [npat, {width}] tensor on {dev}")
+    npat = int(surv.shape[0])
+    if erased.shape[0] != npat:
+        raise ValueError(f"{npat} survivor lists but {erased.shape[0]} erased lists")
+    lds = hip().repair_solve_lds_bytes(n, k, m_pad)
+    if lds < 0:
+        raise ValueError(f"solve_patterns needs 1 <= k <= n <= 256 and 1 <= m_pad <= 256, got ({k}, {n}), m_pad {m_pad}")
+    if lds > 65536:
+        raise NotImplementedError(f"the ({k}, {n}) repair system with m_pad {m_pad} needs {lds} bytes of LDS")
+    for name, t, need, dt in (("coeff_out", coeff_out, npat * m_pad * k, (torch.uint8,)),
+                              ("tables_out", tables_out, npat * k * m_pad * 32, None)):
+        if t is None:
+            continue
+        if t.device != dev or not t.is_contiguous() or (dt and t.dtype not in dt) or t.numel() * t.element_size() < need:
+            raise ValueError(f"{name} must be a contiguous tensor on {dev} of at least {need} bytes")
+    status = torch.empty(npat, dtype=torch.int32, device=dev)
+    st = stream or torch.cuda.current_stream(dev)
+    hip().repair_solve(g_dev.data_ptr(), n, k, surv.data_ptr(), erased.data_ptr(), npat, m_pad,
+                       0 if coeff_out is None else coeff_out.data_ptr(),
+                       0 if tables_out is None else tables_out.data_ptr(), status.data_ptr(), st.cuda_stream)
+    if stream is not None:
+        for t in (g_dev, surv, erased, coeff_out, tables_out, status):
+            if t is not None:
+                t.record_stream(stream)
+    return status
+
+
 def repair_rows(ptrs: np.ndarray, pat: np.ndarray, patterns, m_pad: int) -> tuple[np.ndarray, np.ndarray]:
     """Row addresses of a batched repair: ``ptrs`` the uint64 ``[B, n]`` row addresses of the stripes
     that take part, ``pat`` their ``[B]`` pattern indices. Returns (survivor rows ``[B, k]`` in the
@@ -105,9 +165,16 @@ class BatchRepairPlan:
             the ``e_q x k`` coefficients ``G[erased] . inv(G[survivors])`` over GF(2^8) or ``(e_q, k,
             256)`` GF(2)-linear byte maps (the GF(16) nibble maps).
         check: run the aliasing check (:func:`check_repair_overlap`); False when the caller has.
+        g_dev: the ``(n, k)`` uint8 generator on the stripes' device. With it every pattern is given as
+            ``(survivors_q, erased_q, None)`` and no coefficients come from the host: the descriptor is
+            uploaded with zeroed table blocks and :func:`solve_patterns` writes them in place, launched
+            on the current stream after the upload. The statuses are read back once, here (the only
+            host sync; :meth:`run` has none and is ordered after the solve by the plan's ready event),
+            and kept as ``status`` (int numpy ``[npat]``: 0 built, 1 singular, 2 invalid). A plan with a
+            nonzero status must not be run: the caller checks ``status`` first.
     """
 
-    def __init__(self, stripes, pat, patterns, *, check: bool = True):
+    def __init__(self, stripes, pat, patterns, *, check: bool = True, g_dev: torch.Tensor | None = None):
         if not isinstance(stripes, StripeBatch):
             part = batch_part(stripes, "stripes")
             stripes = StripeBatch(part, part.nrows)
@@ -135,6 +202,14 @@ class BatchRepairPlan:
         keep = pat >= 0
         self.batch = int(keep.sum())
         self.bytewise, self.desc, self._ready = False, None, None
+        self.status, self._unsolved = np.zeros(self.npat, dtype=np.int32), False
+        if g_dev is not None:
+            if any(co is not None for _, _, co in patterns):
+                raise ValueError("with g_dev the patterns carry no coefficients: (survivors, erased, None)")
+            if tuple(g_dev.shape) != (n, self.k) or g_dev.device != self.device:
+                raise ValueError(f"g_dev must be the ({n}, {self.k}) generator on {self.device}")
+        elif any(co is None for _, _, co in patterns):
+            raise ValueError("patterns without coefficients need g_dev")
         if not self.batch:
             return
         ins, outs = repair_rows(stripes.ptrs()[keep], pat[keep], patterns, self.m_pad)
@@ -142,14 +217,29 @@ class BatchRepairPlan:
             check_repair_overlap(ins, outs, self.ncols)
         # one unaligned row: the whole batch bytewise (a padding entry, 0, is aligned)
         self.bytewise = bool((ins % np.uint64(16)).any() or (outs % np.uint64(16)).any())
-        host = build_repair_batch_desc(ins, outs, pat[keep], repair_tables(patterns, self.k, self.m_pad))
+        if g_dev is None:
+            tables = repair_tables(patterns, self.k, self.m_pad)
+        else:  # zeroed blocks, filled by the solve below
+            tables = np.zeros((self.npat, self.k, self.m_pad, 8), dtype=np.uint32)
+        host = build_repair_batch_desc(ins, outs, pat[keep], tables)
         self.desc = torch.from_numpy(host).to(self.device)
+        if g_dev is not None:
+            surv, er = pattern_ids(patterns, self.m_pad)
+            ids = torch.from_numpy(np.concatenate([surv.reshape(-1), er.reshape(-1)])).to(self.device)
+            tab_off = repair_batch_layout(self.k, self.m_pad, self.batch, self.npat)["tab_off"]
+            status = solve_patterns(g_dev, ids[: surv.size].view(self.npat, self.k),
+                                    ids[surv.size:].view(self.npat, self.m_pad), self.m_pad,
+                                    tables_out=self.desc[tab_off:])
+            self.status = status.cpu().numpy()  # the one sync of a device-solved plan
+            self._unsolved = bool(self.status.any())
         self._ready = ready_event(self.device)
 
     def run(self, stream: torch.cuda.Stream | None = None) -> None:
         """Launch over the whole rows on ``stream`` (default: the current stream). No host sync."""
         if not self.batch or not self.ncols:
             return
+        if self._unsolved:
+            raise RuntimeError(f"pattern {int(np.nonzero(self.status)[0][0])} was not solved: its table block is empty")
         st = plan_stream(self, stream)
         if stream is not None:
             self.desc.record_stream(stream)

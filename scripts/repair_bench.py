@@ -21,6 +21,12 @@ call and the loop are apart by more than both spreads. No time is fixed in advan
 
 Without ``--code`` it runs the recorded shapes: 256 x 64 KiB and 256 x 1 MiB at (10, 14) with one and
 four erasures per stripe, and 256 x 64 KiB at (128, 160) with one.
+
+``--fresh`` times what the above leaves out, the FIRST call: ``reconstruct_batch`` on fresh buffers with
+B distinct patterns that nobody has solved (planning plus launch, host clock up to a synchronise) with
+the host solve and with ``device_solve=True``, round by round in turn with the codec's caches emptied,
+then the cached call of both plans, and a single ``reconstruct`` both ways: 256 x 64 KiB at (10, 14)
+with 1 and 4 erasures and at (128, 160) with 1 and 32. ``--device cpu`` runs small shapes end to end.
 """
 from __future__ import annotations
 
@@ -47,6 +53,11 @@ def parse_args(argv=None):
     ap.add_argument("--rounds", type=int, default=9, help="alternations of the timed calls")
     ap.add_argument("--reps", type=int, default=5, help="calls per timed window")
     ap.add_argument("--out", default=None, help="also append the JSON lines here")
+    ap.add_argument("--fresh", action="store_true",
+                    help="time the FIRST reconstruct_batch / reconstruct call on fresh buffers and patterns, with the "
+                         "host solve and with device_solve=True, and the cached call of both")
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
+                    help="with --fresh: cpu runs small shapes end to end (device_solve is ignored there)")
     return ap.parse_args(argv)
 
 
@@ -157,8 +168,157 @@ def bench_shape(torch, k: int, n: int, C: int, B: int, e: int, args) -> dict:
     return res
 
 
+def fresh_patterns(np, n: int, e: int, B: int, seed: int):
+    """``[B, e]`` erased ids, distinct patterns as far as the code has them (C(n, e) < B: reused in turn)."""
+    import itertools
+    import math
+
+    rng = np.random.default_rng(seed)
+    if math.comb(n, e) <= 4 * B:
+        every = list(itertools.combinations(range(n), e))
+        pick = [every[i] for i in rng.permutation(len(every))[:B]]
+    else:
+        pick = set()
+        while len(pick) < B:
+            pick.add(tuple(sorted(int(i) for i in rng.choice(n, size=e, replace=False))))
+        pick = sorted(pick)
+    return np.array([pick[b % len(pick)] for b in range(B)], dtype=np.int64), len(pick)
+
+
+def bench_fresh(torch, k: int, n: int, C: int, B: int, e: int, args) -> dict:
+    """The first ``reconstruct_batch`` call of B stripes with patterns nobody has solved yet (planning
+    plus launch, timed by the host clock up to a device synchronise) with the host solve and with
+    ``device_solve=True``, then the cached call of both plans, round by round in turn; and one
+    ``reconstruct`` of a single stripe both ways. Every round takes fresh buffers and fresh patterns and
+    empties the codec's caches first, so no decode matrix and no plan is reused."""
+    import numpy as np
+
+    from gpu_rscode_amd import ReedSolomon
+
+    dev = args.device
+    rs = ReedSolomon(k, n, matrix=args.matrix)
+    cuda = dev == "cuda"
+    sync = torch.cuda.synchronize if cuda else (lambda: None)
+    torch.manual_seed(1)
+
+    def stripes_for(count):
+        t = torch.zeros((count, n, C), dtype=torch.uint8, device=dev)
+        t[:, :k] = torch.randint(0, 256, (count, k, C), dtype=torch.uint8, device=dev)
+        if cuda:
+            rs.encode_batch(t[:, :k], t[:, k:])
+        else:
+            for b in range(count):
+                rs.encode(t[b, :k], t[b, k:])
+        return t
+
+    def forget():
+        rs._dm.clear()
+        rs._plans.clear()
+
+    def timed(fn):
+        sync()
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def cached(fn):
+        """Per call over ``--reps`` calls of a cached plan: device events on the GPU, else the host clock."""
+        if not cuda:
+            return timed(lambda: [fn() for _ in range(args.reps)]) / args.reps
+        s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        sync()
+        s.record()
+        for _ in range(args.reps):
+            fn()
+        t.record()
+        sync()
+        return s.elapsed_time(t) / args.reps
+
+    good = stripes_for(B)
+    names = ("host_solve", "device_solve")
+    first = {m: [] for m in names}
+    again = {m: [] for m in names}
+    one_first = {m: [] for m in names}
+    one_again = {m: [] for m in names}
+    npat = 0
+    for rnd in range(-1, args.rounds):  # round -1 is the warm-up: code objects, the allocator's blocks
+        erased, npat = fresh_patterns(np, n, e, B, 100 + rnd)
+        for m in names if rnd % 2 else names[::-1]:
+            flag = m == "device_solve"
+            work = good.clone()
+            for b in range(B):
+                work[b, erased[b].tolist()] = 0xEE
+            forget()
+            t_first = timed(lambda: rs.reconstruct_batch(work, erased, device_solve=flag))
+            assert torch.equal(work, good), f"reconstruct_batch({m}) is wrong"
+            t_again = cached(lambda: rs.reconstruct_batch(work, erased, device_solve=flag))
+            one = good[0].clone()
+            ids = erased[0].tolist()
+            one[ids] = 0xEE
+            forget()
+            t_one = timed(lambda: rs.reconstruct(one, ids, device_solve=flag))
+            assert torch.equal(one, good[0]), f"reconstruct({m}) is wrong"
+            t_one_again = cached(lambda: rs.reconstruct(one, ids, device_solve=flag))
+            if rnd >= 0:
+                first[m].append(t_first)
+                again[m].append(t_again)
+                one_first[m].append(t_one)
+                one_again[m].append(t_one_again)
+    res = {"fresh": True, "shape": {"k": k, "n": n, "matrix": args.matrix, "cols": C, "stripes": B, "erasures": e,
+                                    "distinct_patterns": npat},
+           "rounds": args.rounds, "reps": args.reps,
+           "device": torch.cuda.get_device_name(0) if cuda else "cpu (device_solve is ignored there)"}
+    for m in names:
+        res[m] = {"batch_first_call_host_clock": spread(first[m]), "batch_cached_call": spread(again[m]),
+                  "single_first_call_host_clock": spread(one_first[m]), "single_cached_call": spread(one_again[m])}
+    for what, t in (("batch_first_call", first), ("batch_cached_call", again), ("single_first_call", one_first),
+                    ("single_cached_call", one_again)):
+        a, b = t["host_solve"], t["device_solve"]
+        res[f"{what}_host_over_device"] = round(statistics.median(a) / statistics.median(b), 2)
+        res[f"{what}_apart"] = apart(a, b)
+    return res
+
+
+FRESH_SHAPES = "10:14:65536:256:1,10:14:65536:256:4,128:160:65536:256:1,128:160:65536:256:32"
+FRESH_SHAPES_CPU = "10:14:1024:8:1,10:14:1024:8:4,128:160:256:3:1,128:160:256:3:32"
+
+
+def main_fresh(args) -> int:
+    import torch
+
+    if args.device == "cuda" and not torch.cuda.is_available():
+        print("repair_bench.py --fresh --device cuda needs a GPU", file=sys.stderr)
+        return 2
+    if args.code:
+        k, n = (int(v) for v in args.code.split(":"))
+        shapes = [(k, n, args.cols, args.stripes, args.erasures)]
+    else:
+        spec = args.shapes
+        if spec == DEFAULT_SHAPES:
+            spec = FRESH_SHAPES if args.device == "cuda" else FRESH_SHAPES_CPU
+        shapes = [tuple(int(v) for v in s.split(":")) for s in spec.split(",")]
+    lines = []
+    for shape in shapes:
+        line = json.dumps(bench_fresh(torch, *shape, args))
+        print(line, flush=True)
+        lines.append(line)
+        if args.device == "cuda":
+            torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
+    if args.fresh:
+        return main_fresh(args)
+    if args.device != "cuda":
+        print("repair_bench.py --device cpu needs --fresh", file=sys.stderr)
+        return 2
     import torch
 
     if not torch.cuda.is_available():
