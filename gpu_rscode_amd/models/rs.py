@@ -367,9 +367,11 @@ class ReedSolomon:
         pos = {r: j for j, r in enumerate(rows)}
         erased = [i for i in range(self.k) if i not in pos]
         if survivors.device.type != "cuda" or not erased:
-            for r, j in pos.items():
-                if r < self.k:
-                    out[:, r].copy_(survivors[:, j])
+            # (no native erased on the GPU: plain copies, ordered on ``stream`` like the plan's launch)
+            with torch.cuda.stream(stream) if stream is not None and survivors.device.type == "cuda" else null():
+                for r, j in pos.items():
+                    if r < self.k:
+                        out[:, r].copy_(survivors[:, j], non_blocking=True)
             if not erased:
                 return out
             dm = self.decode_matrix(rows)[erased]
@@ -494,8 +496,9 @@ class ReedSolomon:
                 self._cpu_gemm(self._erased_rows(rows, erased), ins, [outs[i] for i in erased])
             return out
         if not erased:  # pure copy: one fused pass with a single dummy output row would waste work
-            for j, r in enumerate(rows):
-                outs[r][:ncols].copy_(ins[j][:ncols], non_blocking=True)
+            with torch.cuda.stream(stream) if stream is not None else null():
+                for j, r in enumerate(rows):
+                    outs[r][:ncols].copy_(ins[j][:ncols], non_blocking=True)
             return out
         key = self._key(("dec", tuple(rows), device_invert), ins, outs)
         if device_invert and self.field == "gf256":

@@ -126,6 +126,14 @@ def ready_event(device: torch.device) -> torch.cuda.Event:
     return ev
 
 
+def contiguous_on(t: torch.Tensor, st: torch.cuda.Stream) -> torch.Tensor:
+    """``t.contiguous()`` with the copy (if one is needed) ordered on ``st``, not on the current stream."""
+    if t.is_contiguous():
+        return t
+    with torch.cuda.stream(st):
+        return t.contiguous()
+
+
 def plan_stream(plan, stream: torch.cuda.Stream | None, *operands: torch.Tensor) -> torch.cuda.Stream:
     """The stream a plan launches on (default: the current one). The plan's first launch waits there
     for ``plan._ready`` (:func:`ready_event`); on a side stream the plan's device ``operands`` are
@@ -305,8 +313,8 @@ class GemmPlan:
             raise ValueError("set_device_coeff applies to engine='mfma' plans")
         if coeff.dtype != torch.uint8 or coeff.device != self.device or coeff.dim() != 2 or coeff.shape[1] < self.k:
             raise ValueError("coeff must be a 2-D uint8 tensor on the plan's device with >= k columns")
-        coeff = coeff.contiguous()
         st = stream or torch.cuda.current_stream(self.device)
+        coeff = contiguous_on(coeff, st)
         sel = 0
         if rows is not None:
             if rows.dtype != torch.int32 or rows.numel() != self.m:
@@ -627,8 +635,8 @@ class Gemm16Plan:
         if coeff.dtype not in (torch.int16, torch.uint16) or coeff.device != self.device or coeff.dim() != 2 \
                 or coeff.shape[1] < self.k:
             raise ValueError("coeff must be a 2-D 16-bit tensor on the plan's device with >= k columns")
-        coeff = coeff.contiguous()
         st = stream or torch.cuda.current_stream(self.device)
+        coeff = contiguous_on(coeff, st)
         sel = 0
         if rows is not None:
             if rows.dtype != torch.int32 or rows.numel() != self.m:

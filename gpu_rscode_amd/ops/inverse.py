@@ -12,7 +12,7 @@ import torch
 
 from ..gf import SingularMatrixError
 from .._native import hip
-from .gemm import Gemm16Plan, GemmPlan
+from .gemm import Gemm16Plan, GemmPlan, contiguous_on
 
 
 def gf_invert(a: torch.Tensor, *, check: bool = True, stream: torch.cuda.Stream | None = None):
@@ -27,11 +27,11 @@ def gf_invert(a: torch.Tensor, *, check: bool = True, stream: torch.cuda.Stream 
     a3 = a.unsqueeze(0) if squeeze else a
     if a3.dim() != 3 or a3.shape[1] != a3.shape[2] or a3.shape[1] > 256:
         raise ValueError("expected (n, n) or (b, n, n) with n <= 256")
-    a3 = a3.contiguous()
+    st = stream or torch.cuda.current_stream(a.device)
+    a3 = contiguous_on(a3, st)
     b, n, _ = a3.shape
     out = torch.empty_like(a3)
     status = torch.empty(b, dtype=torch.int32, device=a.device)
-    st = stream or torch.cuda.current_stream(a.device)
     hip().invert(a3.data_ptr(), out.data_ptr(), n, b, status.data_ptr(), 0, 0, 0, 0, st.cuda_stream)
     if check and bool(status.any().item()):
         bad = torch.nonzero(status).flatten().tolist()
@@ -57,7 +57,7 @@ def invert_into_plan(a: torch.Tensor, plan: GemmPlan, sel_rows, *, status: torch
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=a.device)
     st = stream or torch.cuda.current_stream(a.device)
-    a = a.contiguous()
+    a = contiguous_on(a, st)
     inv = 0
     if plan.engine == "mfma":  # the matrix-core operand is rebuilt from the device inverse too
         if getattr(plan, "_inv_buf", None) is None or plan._inv_buf.shape[0] != n:
@@ -95,7 +95,7 @@ def decode_system_into_plan(g: torch.Tensor, rows: torch.Tensor, erased: torch.T
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=g.device)
     st = stream or torch.cuda.current_stream(g.device)
-    g = g.contiguous()
+    g = contiguous_on(g, st)
     dm = 0
     if plan.engine == "mfma":
         if getattr(plan, "_dm_buf", None) is None or plan._dm_buf.shape != (plan.m, k):
@@ -161,7 +161,7 @@ def decode_system16_into_plan(g: torch.Tensor, rows: torch.Tensor, erased: torch
     if dm is not None and (dm.device != g.device or dm.numel() != e * k or not dm.is_contiguous()):
         raise ValueError("dm must be a contiguous [e, k] 16-bit device tensor")
     st = stream or torch.cuda.current_stream(g.device)
-    g = g.contiguous()
+    g = contiguous_on(g, st)
     if dm is None and plan.engine == "mfma":  # the bit-matrix is rebuilt from the device-solved rows
         if getattr(plan, "_dm_buf", None) is None or plan._dm_buf.shape != (e, k):
             plan._dm_buf = torch.empty((e, k), dtype=torch.int16, device=g.device)
