@@ -99,6 +99,35 @@ constexpr RepairBatchLayout repair_batch_layout(int k, int m_pad, int batch, int
   return l;
 }
 
+// Variable-length batch (csrc/kernels/gf_varlen.hip): repair_batch_layout's record for stripes whose
+// rows differ in length from stripe to stripe, run on a flat grid of `nblk` (stripe, column block)
+// work items:
+//   header {k, m_pad, batch, npat}
+//   in_ptr   [batch * k]      as repair_batch_layout
+//   out_ptr  [batch * m_pad]  as repair_batch_layout
+//   len      [batch]          int64: the row length of stripe b (0: the stripe has no work item)
+//   first_blk[batch]          int64: the exclusive prefix sum of the stripes' block counts
+//   pat      [batch]          int32, pat[b] in [0, npat)
+//   blk_stripe[nblk]          int32: the stripe of work item w; item w is column block
+//                             w - first_blk[blk_stripe[w]] of that stripe
+//   align 32, tab[npat][k][m_pad]   as repair_batch_layout
+// The 8-byte arrays come first so that each array is aligned to its element.
+struct VarlenLayout {
+  size_t in_off, out_off, len_off, first_off, pat_off, blk_off, tab_off, bytes;
+};
+constexpr VarlenLayout varlen_layout(int k, int m_pad, int batch, int npat, int64_t nblk) {
+  VarlenLayout l{};
+  l.in_off = sizeof(DescHeader);
+  l.out_off = l.in_off + 8 * size_t(k) * size_t(batch);
+  l.len_off = l.out_off + 8 * size_t(m_pad) * size_t(batch);
+  l.first_off = l.len_off + 8 * size_t(batch);
+  l.pat_off = l.first_off + 8 * size_t(batch);
+  l.blk_off = l.pat_off + 4 * size_t(batch);
+  l.tab_off = align_up(l.blk_off + 4 * size_t(nblk), 32);
+  l.bytes = l.tab_off + sizeof(PermTable) * size_t(npat) * size_t(k) * size_t(m_pad);
+  return l;
+}
+
 // GF(2^16) descriptor (csrc/kernels/gf_gemm16.hip): the same header and pointer arrays (rows are
 // byte rows holding little-endian 16-bit symbols), and FOUR records per coefficient, tab[j][i][q]
 // with q = 2 * src_byte + dst_byte (gfrs/gf65536.h perm_quad).

@@ -190,6 +190,25 @@ hipError_t launch_gf_update_batched(const void* desc, int k, int d, int m_pad, i
 hipError_t launch_gf_repair_batched(const void* desc, int k, int m_pad, int batch, int npat, int64_t ncols,
                                     bool force_bytewise, hipStream_t stream);
 
+// ---- variable-length batch (csrc/kernels/gf_varlen.hip) -----------------------------------------
+// launch_gf_repair_batched for `batch` stripes whose rows differ in length from stripe to stripe, in
+// ONE launch on a flat grid of `nblk` (stripe, column block) work items: over byte columns
+// [0, len[b]), out_i = XOR_j L_q[i][j](in_j) with q = pat[b]. desc: a varlen_layout(k, m_pad, batch,
+// npat, nblk) record (gfrs/desc.h): in_ptr, out_ptr, pat and the table blocks as in
+// repair_batch_layout, len[b] the row length of stripe b, first_blk the exclusive prefix sum of the
+// stripes' block counts nb[b] = ceil((len[b] / 16 + len[b] % 16) / 256) (force_bytewise:
+// ceil(len[b] / 256)), blk_stripe[w] the stripe of work item w, nblk = sum nb. A stripe of length 0
+// has no work item. The arrays are device data and the caller's duty: the kernel forms addresses from
+// blk_stripe[w] in [0, batch), pat[b] in [0, npat) and first_blk[b] <= w unchecked; a lane touches
+// only columns below len[b]. force_bytewise (any row of any stripe not 16-byte aligned) puts the
+// whole batch on the byte-per-lane form. max_blocks = 0: the default grid (one workgroup per work
+// item up to the grid limit); nonzero: at most that many workgroups, which stride over the work
+// items. No row written may overlap any other row the batch uses. hipErrorInvalidValue, and nothing
+// launched, for a null desc, batch < 1, npat < 1, k outside [1, 256], an m_pad that pad_m does not
+// produce or above 256, nblk < 0 or >= 2^31, or max_blocks < 0; nblk == 0 succeeds without a launch.
+hipError_t launch_gf_varlen(const void* desc, int k, int m_pad, int batch, int npat, int64_t nblk, bool force_bytewise,
+                            int max_blocks, hipStream_t stream);
+
 // ---- device-built repair coefficients (csrc/kernels/gf_repair_solve.hip) ------------------------
 // Solves `npat` erasure patterns of one (n, k) GF(2^8) code in one launch, one workgroup each
 // (grid.x = pattern): g = G (n x k, [I; E]) on the device, surv int32 [npat][k] the survivors of each

@@ -38,29 +38,12 @@
 #include "gfrs/desc.h"
 #include "gfrs/kernels.h"
 #include "gfrs/perm_device.h"
+#include "gfrs/repair_device.h"
 
 namespace gfrs {
 namespace {
 
-using namespace permdev;
-
-// Input rows in flight per lane (16 VGPRs). A ring of 8 holds 90 / 98 / 114 VGPRs (5 / 4 / 4 waves per
-// SIMD) against 58 / 66 / 85 (7 / 7 / 5) and was 12-17 % slower on every shape of profiles/repair.
-constexpr int kRing = 4;
-
-struct RepairView {
-  cptr<uint64_t> in;   // [batch * k]
-  cptr<uint64_t> out;  // [batch * m_pad]
-  cptr<int32_t> pat;   // [batch]
-  cptr<uint32_t> tab;  // [npat][k][m_pad] records
-};
-
-__device__ __forceinline__ uint8_t ldb(uint64_t base, int64_t off) {
-  return __builtin_nontemporal_load((gptr<const uint8_t>)(base + uint64_t(off)));
-}
-__device__ __forceinline__ void stb(uint64_t base, int64_t off, uint8_t v) {
-  __builtin_nontemporal_store(v, (gptr<uint8_t>)(base + uint64_t(off)));
-}
+using namespace repairdev;  // RepairView, kRing, repair_byte (shared with gf_varlen.hip)
 
 // Stripe b = blockIdx.y: its own k input and m_pad output pointers, and the table block of its
 // pattern (returned), all offsets formed in 64 bits and the pattern id moved into an SGPR. Called at
@@ -71,44 +54,6 @@ __device__ __forceinline__ cptr<uint32_t> stripe(RepairView& v, int k, int m_pad
   v.out += b * uint64_t(m_pad);
   const int q = sgpr_int(v.pat[b]);
   return v.tab + uint64_t(uint32_t(q)) * uint64_t(k) * uint64_t(m_pad) * uint64_t(kPermStride);
-}
-
-// One byte column at row offset `off` (rows of any alignment): the ragged tail of the vector form
-// and every lane of the byte form. The row bytes are loaded 8 at a time before any is used (as
-// gf_gemm.hip's tail_byte); tiles of up to 4 outputs, a tile without an output row skipped.
-__device__ __forceinline__ void repair_byte(const RepairView& v, cptr<uint32_t> tb, int k, int m_pad, int64_t off) {
-  constexpr int kB = 8;
-  for (int i0 = 0; i0 < m_pad; i0 += 4) {
-    uint64_t op[4];
-    uint32_t acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      op[i] = i0 + i < m_pad ? v.out[i0 + i] : 0;  // (0: a padding output, never touched)
-      acc[i] = 0;
-    }
-    if (!(op[0] | op[1] | op[2] | op[3])) continue;
-    for (int j0 = 0; j0 < k; j0 += kB) {
-      uint32_t x[kB];
-#pragma unroll
-      for (int u = 0; u < kB; ++u) x[u] = j0 + u < k ? uint32_t(ldb(v.in[j0 + u], off)) : 0u;
-#pragma unroll
-      for (int u = 0; u < kB; ++u) {
-        const int j = j0 + u;
-        if (j < k) {
-          const Sel s = make_sel(x[u]);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            // a slot past m_pad applies row m_pad - 1's map to an accumulator nobody stores
-            const int ii = std::min(i0 + i, m_pad - 1);
-            acc[i] = mac_map(acc[i], tb + (size_t(j) * m_pad + ii) * kPermStride, s);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (op[i]) stb(op[i], off, uint8_t(acc[i]));
-  }
 }
 
 // Vector form. MT = output rows per tile = min(4, m_pad), so m_pad is a multiple of MT and every
@@ -125,61 +70,7 @@ __global__ __launch_bounds__(kBlock) void gf_repair_vec_kernel(RepairView v, int
       if (g - ngroups < tail) repair_byte(v, tb, k, m_pad, ngroups * 16 + (g - ngroups));
       continue;
     }
-    const int64_t off = g * 16;
-    for (int i0 = 0; i0 < m_pad; i0 += MT) {
-      uint64_t op[MT], any = 0;
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        op[i] = v.out[i0 + i];
-        any |= op[i];
-      }
-      if (!any) continue;  // (wave-uniform: this stripe has fewer erasures than the widest pattern)
-
-      uint32_t acc[MT][4];
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[i][w] = 0;
-
-      u32x4 ring[kRing];
-#pragma unroll
-      for (int u = 0; u < kRing; ++u)
-        if (u < k) ring[u] = ld16<true>(row_vec(v.in[u], off));
-
-      for (int j0 = 0; j0 < k; j0 += kRing) {
-#pragma unroll
-        for (int u = 0; u < kRing; u += 2) {
-          const int j = j0 + u;
-          if (j + 1 < k) {
-            const u32x4 x0 = ring[u], x1 = ring[u + 1];
-            if (j + kRing < k) ring[u] = ld16<true>(row_vec(v.in[j + kRing], off));
-            if (j + 1 + kRing < k) ring[u + 1] = ld16<true>(row_vec(v.in[j + 1 + kRing], off));
-            const auto t0 = tb + (size_t(j) * m_pad + i0) * kPermStride;
-            const auto t1 = t0 + size_t(m_pad) * kPermStride;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const Sel s0 = make_sel(x0[w]);
-              const Sel s1 = make_sel(x1[w]);
-#pragma unroll
-              for (int i = 0; i < MT; ++i)
-                acc[i][w] = mac_pair(acc[i][w], t0 + i * kPermStride, s0, t1 + i * kPermStride, s1);
-            }
-          } else if (j < k) {
-            const u32x4 x = ring[u];
-            const auto t = tb + (size_t(j) * m_pad + i0) * kPermStride;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const Sel s = make_sel(x[w]);
-#pragma unroll
-              for (int i = 0; i < MT; ++i) acc[i][w] = mac_map(acc[i][w], t + i * kPermStride, s);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-        if (op[i]) st16<true>(row_vec_w(op[i], off), u32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]});
-    }
+#include "gfrs/repair_group_body.h"
   }
 }
 

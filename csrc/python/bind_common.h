@@ -121,6 +121,19 @@ inline void bind_common(py::module_& m) {
     r["bytes"] = l.bytes;
     return r;
   }, py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"));
+  m.def("varlen_layout", [](int k, int m_pad, int batch, int npat, int64_t nblk) {
+    const gfrs::VarlenLayout l = gfrs::varlen_layout(k, m_pad, batch, npat, nblk);
+    py::dict r;
+    r["in_off"] = l.in_off;
+    r["out_off"] = l.out_off;
+    r["len_off"] = l.len_off;
+    r["first_off"] = l.first_off;
+    r["pat_off"] = l.pat_off;
+    r["blk_off"] = l.blk_off;
+    r["tab_off"] = l.tab_off;
+    r["bytes"] = l.bytes;
+    return r;
+  }, py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("nblk"));
   m.def("desc_layout16", [](int k, int m_pad, int batch) {
     const gfrs::DescLayout l = gfrs::desc_layout16(k, m_pad, batch);
     py::dict d;

@@ -249,6 +249,16 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("ncols"),
       py::arg("bytewise"), py::arg("stream") = 0);
   m.def(
+      "varlen",
+      [](uint64_t desc, int k, int m_pad, int batch, int npat, int64_t nblk, bool bytewise, int max_blocks,
+         uint64_t stream) {
+        check(launch_gf_varlen(reinterpret_cast<const void*>(desc), k, m_pad, batch, npat, nblk, bytewise, max_blocks,
+                               as_stream(stream)),
+              "gf_varlen");
+      },
+      py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("nblk"),
+      py::arg("bytewise"), py::arg("max_blocks") = 0, py::arg("stream") = 0);
+  m.def(
       "repair_solve",
       [](uint64_t g, int n, int k, uint64_t surv, uint64_t erased, int npat, int m_pad, uint64_t coeff, uint64_t tab,
          uint64_t status, uint64_t stream) {
