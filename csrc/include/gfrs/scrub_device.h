@@ -1,7 +1,8 @@
 // What the kernels over a scrub descriptor share (gf_scrub.hip, gf_correct.hip, gf_checked.hip): the
 // per-lane syndrome of a column unit, the hot pass's fold of row bits into the mask and its grid,
-// the workgroup span, the tile dispatch and the argument rules of their launchers. Include from a
-// .hip file only.
+// the cold pass's scaffold (stripe offsets, span, column sweep, count flush), the tile dispatch, the
+// argument rules of their launchers and the slicing of a batch past the grid.y limit. The decoder of
+// the cold passes that repair is in correct_device.h. Include from a .hip file only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,6 +93,72 @@ inline Grid make_grid(int64_t items, int ntiles) {
 constexpr int kLocSpanShift = 14;  // a workgroup covers min(block_bytes, 16 KiB) columns
 constexpr int kMaxGridY = 65535;   // stripes per launch, as launch_gf_gemm_batched
 
+// mask words of one stripe: one per block of 2^bshift columns
+__host__ __device__ inline int64_t mask_words(int64_t ncols, int bshift) {
+  return (ncols + (int64_t(1) << bshift) - 1) >> bshift;
+}
+
+// ---- the cold pass over dirty blocks (gf_locate_kernel, gf_correct_kernel, gf_checked_fix_kernel) ----
+// One workgroup per span of min(block_bytes, 16 KiB) columns, grid.x = span.
+struct Span {
+  int64_t base, end;  // the workgroup's columns
+  bool dirty;         // its mask word is nonzero
+};
+
+// Stripe b = blockIdx.y of a batched launch (its own n_in input and n_out output row pointers, mask
+// row and nbins counts, every offset formed in 64 bits), then the workgroup's span. n_out = 0: the
+// kernel stores no output rows and d.out stays as it is. `dirty` is uniform, so on !dirty the whole
+// workgroup can leave, before any barrier.
+template <bool BATCH>
+__device__ __forceinline__ Span cold_span(DescView& d, int n_in, int n_out, const int*& mask,
+                                          unsigned long long*& counts, int nbins, int64_t ncols, int bshift,
+                                          int span_shift) {
+  if constexpr (BATCH) {
+    const uint64_t b = blockIdx.y;
+    d.in += b * uint64_t(n_in);
+    d.out += b * uint64_t(n_out);
+    mask += b * uint64_t(mask_words(ncols, bshift));
+    counts += b * uint64_t(nbins);
+  }
+  const int64_t base = int64_t(blockIdx.x) << span_shift;
+  return {base, std::min(base + (int64_t(1) << span_shift), ncols), mask[base >> bshift] != 0};
+}
+
+// col(acc, q, c) for every column c of the span: its syndrome bytes are byte q of acc[0..MT-1] under
+// the MT-row tables of `d` over n input rows. Four columns per lane, the ragged end of the span a
+// byte at a time; `bytewise` (rows of any alignment): one column per lane throughout.
+template <int MT, typename F>
+__device__ __forceinline__ void sweep_span(const DescView& d, int n, const Span& s, bool bytewise, F&& col) {
+  uint32_t acc[MT];
+  if (!bytewise) {
+    for (int64_t c = s.base + int64_t(threadIdx.x) * 4; c < s.end; c += kBlock * 4) {
+      if (c + 4 <= s.end) {
+        syn_cols<MT, uint32_t>(d, n, MT, 0, c, acc);
+        for (int q = 0; q < 4; ++q) col(acc, q, c + q);
+      } else {
+        for (int64_t cc = c; cc < s.end; ++cc) {
+          syn_cols<MT, uint8_t>(d, n, MT, 0, cc, acc);
+          col(acc, 0, cc);
+        }
+      }
+    }
+  } else {
+    for (int64_t c = s.base + threadIdx.x; c < s.end; c += kBlock) {
+      syn_cols<MT, uint8_t>(d, n, MT, 0, c, acc);
+      col(acc, 0, c);
+    }
+  }
+}
+
+// The workgroup's LDS histogram into the stripe's 64-bit counts: one atomic add per nonzero bin
+__device__ __forceinline__ void flush_bins(const uint32_t* hist, int nbins, unsigned long long* counts) {
+  __syncthreads();
+  for (int t = threadIdx.x; t < nbins; t += kBlock) {
+    const uint32_t v = hist[t];
+    if (v) atomicAdd(counts + t, (unsigned long long)v);
+  }
+}
+
 template <typename F>
 hipError_t dispatch_tile(int t, F&& f) {
   switch (t) {
@@ -118,6 +185,38 @@ inline bool locate_args_ok(int n, int p, int64_t ncols, int64_t block_bytes) {
   if (p < 1 || p > 16 || p >= n || !scrub_args_ok(n, pad_m(p), ncols, block_bytes)) return false;
   const int span_shift = std::min(log2_exact(block_bytes), kLocSpanShift);
   return ((ncols + (int64_t(1) << span_shift) - 1) >> span_shift) <= int64_t(INT32_MAX);
+}
+
+// ---- launchers ----
+
+// A batch in slices of at most kMaxGridY stripes (grid.y): launch(d, stripes, mask, counts) gets the
+// descriptor view, mask row and counts row of its first stripe. The strides are per stripe: input and
+// output row pointers, mask words, count words (counts may be null, with a stride of 0). The first
+// error ends it.
+template <typename Mask, typename F>
+hipError_t launch_slices(const DescView& d0, int batch, size_t in_stride, size_t out_stride, Mask* mask,
+                         size_t mask_stride, uint64_t* counts, size_t count_stride, F&& launch) {
+  hipError_t e = hipSuccess;
+  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
+    DescView d = d0;
+    d.in += size_t(b0) * in_stride;
+    d.out += size_t(b0) * out_stride;
+    e = launch(d, unsigned(std::min(batch - b0, kMaxGridY)), mask + size_t(b0) * mask_stride,
+               counts + size_t(b0) * count_stride);
+  }
+  return e;
+}
+
+// One cold launch over `batch` stripes: kernel(mt, grid, span_shift) launches the family's kernel
+// for the tile of pad_m(rows) check rows.
+template <typename F>
+hipError_t cold_launch(int rows, unsigned batch, int64_t ncols, int bshift, F&& kernel) {
+  const int span_shift = std::min(bshift, kLocSpanShift);
+  const int64_t nwg = (ncols + (int64_t(1) << span_shift) - 1) >> span_shift;
+  return dispatch_tile(pad_m(rows), [&](auto mt) -> hipError_t {
+    kernel(mt, dim3(unsigned(nwg), batch), span_shift);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace scrubdev

@@ -18,7 +18,9 @@
 // Both have a batched form (template flag BATCH, grid.y = stripe) over a desc_layout(n, m_pad, batch)
 // descriptor, for scrubbing many small stripes in one launch: stripe b reads its own row pointers and
 // writes its own mask and counts rows; the tables of H are shared. The single-stripe launchers run
-// the BATCH = false instantiations, which the flag leaves exactly as they were.
+// the BATCH = false instantiations, which the flag leaves exactly as they were. The cold pass's
+// scaffold (stripe offsets, span and early exit, column sweep, count flush) and the launchers' slicing
+// of a batch past the grid.y limit are scrub_device.h's, shared with gf_correct.hip and gf_checked.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,7 +37,7 @@ namespace gfrs {
 namespace {
 
 using namespace permdev;
-using namespace scrubdev;  // syn_cols, the locate span, dispatch_tile and the argument rules (shared with gf_correct.hip)
+using namespace scrubdev;
 
 __constant__ Tables d_tab = make_tables();
 
@@ -277,19 +279,13 @@ __device__ __forceinline__ void classify(const LocLds& l, uint32_t* hist, const 
 }
 
 // BATCH: grid.y = stripe; the stripe's own rows, mask row and n + 2 counts (histogram and totals
-// are per stripe). A workgroup whose stripe's mask word is zero still leaves before any barrier.
+// are per stripe).
 template <int MT, bool BATCH = false>
 __global__ __launch_bounds__(kBlock) void gf_locate_kernel(DescView d, int n, int p, int64_t ncols, int bshift,
                                                            int span_shift, const int* mask, const uint8_t* loc,
                                                            int locatable, int bytewise, unsigned long long* counts) {
-  if constexpr (BATCH) {
-    const uint64_t b = blockIdx.y;
-    d.in += b * uint64_t(n);
-    mask += b * uint64_t((ncols + (int64_t(1) << bshift) - 1) >> bshift);
-    counts += b * uint64_t(n + 2);
-  }
-  const int64_t base = int64_t(blockIdx.x) << span_shift;
-  if (mask[base >> bshift] == 0) return;  // (uniform: the whole workgroup leaves before any barrier)
+  const Span span = cold_span<BATCH>(d, n, 0, mask, counts, n + 2, ncols, bshift, span_shift);
+  if (!span.dirty) return;
   __shared__ LocLds l;
   for (int t = threadIdx.x; t < 1024; t += kBlock) l.exp[t] = t < kExpLen ? d_tab.exp[t] : uint8_t(0);
   for (int t = threadIdx.x; t < 256; t += kBlock) l.log[t] = d_tab.log[t];
@@ -301,34 +297,13 @@ __global__ __launch_bounds__(kBlock) void gf_locate_kernel(DescView d, int n, in
   for (int t = threadIdx.x; t < n + 2; t += kBlock) l.hist[t] = 0;
   __syncthreads();
 
-  const int64_t end = std::min(base + (int64_t(1) << span_shift), ncols);
   uint32_t bad = 0, unl = 0;
-  uint32_t acc[MT];
-  if (!bytewise) {
-    for (int64_t c = base + int64_t(threadIdx.x) * 4; c < end; c += kBlock * 4) {
-      if (c + 4 <= end) {
-        syn_cols<MT, uint32_t>(d, n, MT, 0, c, acc);
-        for (int q = 0; q < 4; ++q) classify<MT>(l, l.hist, acc, q, n, p, locatable != 0, bad, unl);
-      } else {
-        for (int64_t cc = c; cc < end; ++cc) {
-          syn_cols<MT, uint8_t>(d, n, MT, 0, cc, acc);
-          classify<MT>(l, l.hist, acc, 0, n, p, locatable != 0, bad, unl);
-        }
-      }
-    }
-  } else {
-    for (int64_t c = base + threadIdx.x; c < end; c += kBlock) {
-      syn_cols<MT, uint8_t>(d, n, MT, 0, c, acc);
-      classify<MT>(l, l.hist, acc, 0, n, p, locatable != 0, bad, unl);
-    }
-  }
+  sweep_span<MT>(d, n, span, bytewise != 0, [&](const uint32_t (&acc)[MT], int q, int64_t) {
+    classify<MT>(l, l.hist, acc, q, n, p, locatable != 0, bad, unl);
+  });
   if (unl) atomicAdd(&l.hist[n], unl);
   if (bad) atomicAdd(&l.hist[n + 1], bad);
-  __syncthreads();
-  for (int t = threadIdx.x; t < n + 2; t += kBlock) {
-    const uint32_t v = l.hist[t];
-    if (v) atomicAdd(counts + t, (unsigned long long)v);
-  }
+  flush_bins(l.hist, n + 2, counts);
 }
 
 // ---- launch -----------------------------------------------------------------------------------
@@ -368,105 +343,84 @@ bool launch_rows(const DescView& d, int n, int m_pad, int ident, const Grid& g, 
   return false;
 }
 
-// One syndrome launch over `batch` stripes (grid.y); `d` and `mask` are those of the first of them.
+// One family for each pair of launchers (the single one is the BATCH = false instantiation on a
+// batch of one): the mask or the counts cleared, then the batch in slices of grid.y stripes.
 template <bool BATCH>
-hipError_t syndrome_launch(const DescView& d, int n, int m_pad, int ident, unsigned batch, int64_t ncols,
-                           bool force_bytewise, int bshift, int* mask, hipStream_t stream) {
-  return dispatch_tile(tile_for(m_pad), [&](auto mt) -> hipError_t {
-    constexpr int MT = decltype(mt)::value;
-    const int ntiles = m_pad / MT;
-    if (force_bytewise) {
-      const Grid g = make_grid(ncols, ntiles);
-      gf_syndrome_byte_kernel<MT, BATCH>
-          <<<dim3(g.blocks, batch), kBlock, 0, stream>>>(d, n, m_pad, ntiles, ncols, g.nblk, g.ncb, mask, bshift);
-      return hipGetLastError();
-    }
-    const int64_t ngroups = ncols / 16;
-    const int tail = int(ncols % 16);
-    const Grid g = make_grid(ngroups + tail, ntiles);  // one extra lane per ragged tail byte
-    if (!launch_rows<MT, BATCH>(d, n, m_pad, ident, g, batch, ngroups, tail, mask, bshift, stream))
-      gf_syndrome_vec_kernel<MT, BATCH><<<dim3(g.blocks, batch), kBlock, 0, stream>>>(d, n, m_pad, ntiles, ngroups,
-                                                                                      g.nblk, g.ncb, tail, mask, bshift);
-    return hipGetLastError();
-  });
+hipError_t syndrome_all(const void* desc, int n, int m_pad, int ident, int batch, int64_t ncols, bool force_bytewise,
+                        int64_t block_bytes, int32_t* mask, hipStream_t stream) {
+  if (!scrub_args_ok(n, m_pad, ncols, block_bytes) || !mask || ident < 0 || ident > m_pad || ident >= n)
+    return hipErrorInvalidValue;
+  if (ncols == 0) return hipSuccess;
+  const int bshift = log2_exact(block_bytes);
+  const int64_t nmask = mask_words(ncols, bshift);
+  const hipError_t e = hipMemsetAsync(mask, 0, size_t(batch) * size_t(nmask) * sizeof(int32_t), stream);
+  if (e != hipSuccess) return e;
+  return launch_slices(
+      view(desc, n, m_pad, batch), batch, n, 0, mask, nmask, nullptr, 0,
+      [&](const DescView& d, unsigned stripes, int32_t* m, uint64_t*) {
+        return dispatch_tile(tile_for(m_pad), [&](auto mt) -> hipError_t {
+          constexpr int MT = decltype(mt)::value;
+          const int ntiles = m_pad / MT;
+          if (force_bytewise) {
+            const Grid g = make_grid(ncols, ntiles);
+            gf_syndrome_byte_kernel<MT, BATCH>
+                <<<dim3(g.blocks, stripes), kBlock, 0, stream>>>(d, n, m_pad, ntiles, ncols, g.nblk, g.ncb, m, bshift);
+            return hipGetLastError();
+          }
+          const int64_t ngroups = ncols / 16;
+          const int tail = int(ncols % 16);
+          const Grid g = make_grid(ngroups + tail, ntiles);  // one extra lane per ragged tail byte
+          if (!launch_rows<MT, BATCH>(d, n, m_pad, ident, g, stripes, ngroups, tail, m, bshift, stream))
+            gf_syndrome_vec_kernel<MT, BATCH><<<dim3(g.blocks, stripes), kBlock, 0, stream>>>(
+                d, n, m_pad, ntiles, ngroups, g.nblk, g.ncb, tail, m, bshift);
+          return hipGetLastError();
+        });
+      });
 }
 
 template <bool BATCH>
-hipError_t locate_launch(const DescView& d, int n, int p, unsigned batch, int64_t ncols, bool force_bytewise,
-                         int bshift, const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
-                         hipStream_t stream) {
-  const int span_shift = std::min(bshift, kLocSpanShift);
-  const int64_t nwg = (ncols + (int64_t(1) << span_shift) - 1) >> span_shift;
-  return dispatch_tile(pad_m(p), [&](auto mt) -> hipError_t {
-    constexpr int MT = decltype(mt)::value;
-    gf_locate_kernel<MT, BATCH><<<dim3(unsigned(nwg), batch), kBlock, 0, stream>>>(
-        d, n, p, ncols, bshift, span_shift, mask, loc, locatable ? 1 : 0, force_bytewise ? 1 : 0,
-        reinterpret_cast<unsigned long long*>(counts));
-    return hipGetLastError();
-  });
+hipError_t locate_all(const void* desc, int n, int p, int batch, int64_t ncols, bool force_bytewise,
+                      int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
+                      hipStream_t stream) {
+  if (!locate_args_ok(n, p, ncols, block_bytes) || !mask || !loc || !counts) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(counts, 0, size_t(batch) * size_t(n + 2) * sizeof(uint64_t), stream);
+  if (e != hipSuccess || ncols == 0) return e;
+  const int bshift = log2_exact(block_bytes);
+  return launch_slices(
+      view(desc, n, pad_m(p), batch), batch, n, 0, mask, mask_words(ncols, bshift), counts, n + 2,
+      [&](const DescView& d, unsigned stripes, const int32_t* m, uint64_t* c) {
+        return cold_launch(p, stripes, ncols, bshift, [&](auto mt, dim3 grid, int span_shift) {
+          gf_locate_kernel<decltype(mt)::value, BATCH><<<grid, kBlock, 0, stream>>>(
+              d, n, p, ncols, bshift, span_shift, m, loc, locatable ? 1 : 0, force_bytewise ? 1 : 0,
+              reinterpret_cast<unsigned long long*>(c));
+        });
+      });
 }
 
 }  // namespace
 
 hipError_t launch_gf_syndrome(const void* desc, int n, int m_pad, int ident, int64_t ncols, bool force_bytewise,
                               int64_t block_bytes, int32_t* mask, hipStream_t stream) {
-  if (!scrub_args_ok(n, m_pad, ncols, block_bytes) || !mask || ident < 0 || ident > m_pad || ident >= n)
-    return hipErrorInvalidValue;
-  if (ncols == 0) return hipSuccess;
-  const int bshift = log2_exact(block_bytes);
-  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
-  hipError_t e = hipMemsetAsync(mask, 0, size_t(nmask) * sizeof(int32_t), stream);
-  if (e != hipSuccess) return e;
-  return syndrome_launch<false>(view(desc, n, m_pad), n, m_pad, ident, 1, ncols, force_bytewise, bshift, mask, stream);
+  return syndrome_all<false>(desc, n, m_pad, ident, 1, ncols, force_bytewise, block_bytes, mask, stream);
 }
 
 hipError_t launch_gf_syndrome_batched(const void* desc, int n, int m_pad, int ident, int batch, int64_t ncols,
                                       bool force_bytewise, int64_t block_bytes, int32_t* mask, hipStream_t stream) {
-  if (batch < 1 || !desc || !scrub_args_ok(n, m_pad, ncols, block_bytes) || !mask || ident < 0 || ident > m_pad ||
-      ident >= n)
-    return hipErrorInvalidValue;
-  if (ncols == 0) return hipSuccess;
-  const int bshift = log2_exact(block_bytes);
-  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
-  hipError_t e = hipMemsetAsync(mask, 0, size_t(batch) * size_t(nmask) * sizeof(int32_t), stream);
-  const DescView d0 = view(desc, n, m_pad, batch);
-  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
-    DescView d = d0;
-    d.in += size_t(b0) * size_t(n);
-    e = syndrome_launch<true>(d, n, m_pad, ident, unsigned(std::min(batch - b0, kMaxGridY)), ncols, force_bytewise,
-                              bshift, mask + size_t(b0) * size_t(nmask), stream);
-  }
-  return e;
+  if (batch < 1 || !desc) return hipErrorInvalidValue;
+  return syndrome_all<true>(desc, n, m_pad, ident, batch, ncols, force_bytewise, block_bytes, mask, stream);
 }
 
 hipError_t launch_gf_locate(const void* desc, int n, int p, int64_t ncols, bool force_bytewise, int64_t block_bytes,
                             const int32_t* mask, const uint8_t* loc, bool locatable, uint64_t* counts,
                             hipStream_t stream) {
-  if (!locate_args_ok(n, p, ncols, block_bytes) || !mask || !loc || !counts) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(counts, 0, size_t(n + 2) * sizeof(uint64_t), stream);
-  if (e != hipSuccess || ncols == 0) return e;
-  return locate_launch<false>(view(desc, n, pad_m(p)), n, p, 1, ncols, force_bytewise, log2_exact(block_bytes), mask,
-                              loc, locatable, counts, stream);
+  return locate_all<false>(desc, n, p, 1, ncols, force_bytewise, block_bytes, mask, loc, locatable, counts, stream);
 }
 
 hipError_t launch_gf_locate_batched(const void* desc, int n, int p, int batch, int64_t ncols, bool force_bytewise,
                                     int64_t block_bytes, const int32_t* mask, const uint8_t* loc, bool locatable,
                                     uint64_t* counts, hipStream_t stream) {
-  if (batch < 1 || !desc || !locate_args_ok(n, p, ncols, block_bytes) || !mask || !loc || !counts)
-    return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(counts, 0, size_t(batch) * size_t(n + 2) * sizeof(uint64_t), stream);
-  if (ncols == 0) return e;
-  const int bshift = log2_exact(block_bytes);
-  const int64_t nmask = (ncols + block_bytes - 1) >> bshift;
-  const DescView d0 = view(desc, n, pad_m(p), batch);
-  for (int b0 = 0; b0 < batch && e == hipSuccess; b0 += kMaxGridY) {
-    DescView d = d0;
-    d.in += size_t(b0) * size_t(n);
-    e = locate_launch<true>(d, n, p, unsigned(std::min(batch - b0, kMaxGridY)), ncols, force_bytewise, bshift,
-                            mask + size_t(b0) * size_t(nmask), loc, locatable, counts + size_t(b0) * size_t(n + 2),
-                            stream);
-  }
-  return e;
+  if (batch < 1 || !desc) return hipErrorInvalidValue;
+  return locate_all<true>(desc, n, p, batch, ncols, force_bytewise, block_bytes, mask, loc, locatable, counts, stream);
 }
 
 }  // namespace gfrs
