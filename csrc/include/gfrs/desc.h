@@ -128,6 +128,38 @@ constexpr VarlenLayout varlen_layout(int k, int m_pad, int batch, int npat, int6
   return l;
 }
 
+// Variable-length scrub (csrc/kernels/gf_varlen_scrub.hip): the n rows of `batch` stripes of differing
+// lengths, the tables of the check matrix H (shared, no patterns, no outputs) and two flat work lists:
+// `nblk` (stripe, column block) items of the hot pass, as varlen_layout's, and `nspan` (stripe, span)
+// items of the cold pass, a span being min(block_bytes, 16 KiB) columns:
+//   header {n, m_pad, batch, 0}
+//   in_ptr    [batch * n]   stripe b's rows at [b*n + j], natives first
+//   len       [batch]       int64: the row length of stripe b (0: no work item of either kind)
+//   first_blk [batch]       int64: the exclusive prefix sum of the stripes' block counts
+//   first_span[batch]       int64: the exclusive prefix sum of the stripes' span counts
+//   mask_first[batch]       int64: the exclusive prefix sum of ceil(len / block_bytes): stripe b's
+//                           first word in the mask
+//   align 32, tab[n][m_pad] PermTable records of H, tab[j][i] = the map of H[i][j]
+//   blk_stripe [nblk]       int32: the stripe of hot work item w
+//   span_stripe[nspan]      int32: the stripe of cold work item w
+// The tables stand before the two lists so that neither pass needs the other's item count to find them.
+struct VarlenScrubLayout {
+  size_t in_off, len_off, first_off, span_first_off, mask_first_off, tab_off, blk_off, span_off, bytes;
+};
+constexpr VarlenScrubLayout varlen_scrub_layout(int n, int m_pad, int batch, int64_t nblk, int64_t nspan) {
+  VarlenScrubLayout l{};
+  l.in_off = sizeof(DescHeader);
+  l.len_off = l.in_off + 8 * size_t(n) * size_t(batch);
+  l.first_off = l.len_off + 8 * size_t(batch);
+  l.span_first_off = l.first_off + 8 * size_t(batch);
+  l.mask_first_off = l.span_first_off + 8 * size_t(batch);
+  l.tab_off = align_up(l.mask_first_off + 8 * size_t(batch), 32);
+  l.blk_off = l.tab_off + sizeof(PermTable) * size_t(n) * size_t(m_pad);
+  l.span_off = l.blk_off + 4 * size_t(nblk);
+  l.bytes = l.span_off + 4 * size_t(nspan);
+  return l;
+}
+
 // GF(2^16) descriptor (csrc/kernels/gf_gemm16.hip): the same header and pointer arrays (rows are
 // byte rows holding little-endian 16-bit symbols), and FOUR records per coefficient, tab[j][i][q]
 // with q = 2 * src_byte + dst_byte (gfrs/gf65536.h perm_quad).

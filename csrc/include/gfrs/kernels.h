@@ -209,6 +209,35 @@ hipError_t launch_gf_repair_batched(const void* desc, int k, int m_pad, int batc
 hipError_t launch_gf_varlen(const void* desc, int k, int m_pad, int batch, int npat, int64_t nblk, bool force_bytewise,
                             int max_blocks, hipStream_t stream);
 
+// ---- variable-length scrub (csrc/kernels/gf_varlen_scrub.hip) ------------------------------------
+// launch_gf_syndrome_batched / launch_gf_locate_batched for `batch` stripes whose rows differ in length
+// from stripe to stripe, each pass ONE launch on a flat grid. desc: a varlen_scrub_layout(n, m_pad,
+// batch, nblk, nspan) record (gfrs/desc.h): stripe b's n rows, len[b], the tables of H (m_pad =
+// pad_m(p), shared), and per pass a work list: blk_stripe / first_blk over nblk (stripe, column block)
+// items as launch_gf_varlen's (force_bytewise picks the byte-per-lane counts), span_stripe /
+// first_span over nspan (stripe, span) items, ns[b] = ceil(len[b] / min(block_bytes, 16 KiB)); and
+// mask_first[b], the exclusive prefix sum of ceil(len[b] / block_bytes). A stripe of length 0 has no
+// item and no mask word. The arrays are device data and the caller's duty, read unchecked.
+// mask: nwords = sum ceil(len[b] / block_bytes) block words, stripe b's from mask_first[b], each as
+// launch_gf_syndrome defines it, then `batch` stripe words, word b the OR of stripe b's block words:
+// one allocation, zeroed here by one memset (on a stream under graph capture: by a kernel node); a
+// consistent batch stores nothing else. A work item walks
+// every output tile of its columns, so any p up to 256 runs. ident as launch_gf_syndrome. max_blocks
+// as launch_gf_varlen. hipErrorInvalidValue with nothing launched or written for a null desc or mask,
+// batch < 1, n outside [1, 256], an m_pad that pad_m does not produce or above 256, ident outside
+// [0, m_pad] or >= n, a block_bytes that is not a power of two >= 4096, nblk outside [0, 2^31),
+// nwords < 0 or max_blocks < 0; nblk == 0 succeeds after the memset.
+hipError_t launch_gf_varlen_syndrome(const void* desc, int n, int m_pad, int ident, int batch, int64_t nblk,
+                                     int64_t block_bytes, bool force_bytewise, int max_blocks, int32_t* mask,
+                                     int64_t nwords, hipStream_t stream);
+// The cold pass over the same record and mask (p <= 16): every byte column of the spans whose block
+// word is nonzero is classified as launch_gf_locate does, into counts + b * (n + 2), all zeroed here
+// by one memset. Refused as above, and for a null loc or counts, p outside [1, 16] or >= n, and nspan
+// outside [0, 2^31); nspan == 0 succeeds after the memset.
+hipError_t launch_gf_varlen_locate(const void* desc, int n, int p, int batch, int64_t nblk, int64_t nspan,
+                                   int64_t block_bytes, bool force_bytewise, int max_blocks, const int32_t* mask,
+                                   const uint8_t* loc, bool locatable, uint64_t* counts, hipStream_t stream);
+
 // ---- device-built repair coefficients (csrc/kernels/gf_repair_solve.hip) ------------------------
 // Solves `npat` erasure patterns of one (n, k) GF(2^8) code in one launch, one workgroup each
 // (grid.x = pattern): g = G (n x k, [I; E]) on the device, surv int32 [npat][k] the survivors of each

@@ -44,6 +44,17 @@ __device__ __forceinline__ void syn_cols(const DescView& d, int n, int m_pad, in
   }
 }
 
+// bit i: syndrome row i0 + i is nonzero in this byte column
+template <int MT>
+__device__ __forceinline__ uint32_t syn_byte_bits(const DescView& d, int n, int m_pad, int i0, int64_t off) {
+  uint32_t acc[MT];
+  syn_cols<MT, uint8_t>(d, n, m_pad, i0, off, acc);
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) bits |= uint32_t((acc[i] & 0xFFu) != 0) << i;
+  return bits;
+}
+
 // ---- the hot pass: row bits of a lane's accumulators into the mask (gf_scrub.hip, gf_checked.hip) ----
 template <int MT>
 __device__ __forceinline__ uint32_t group_bits(const uint32_t (&acc)[MT][4]) {
@@ -157,6 +168,63 @@ __device__ __forceinline__ void flush_bins(const uint32_t* hist, int nbins, unsi
     const uint32_t v = hist[t];
     if (v) atomicAdd(counts + t, (unsigned long long)v);
   }
+}
+
+// ---- locate: the classifier of gf_locate_kernel and gf_varlen_locate_kernel ----
+struct LocLds {
+  uint8_t exp[1024];         // gf256.h layout: exp[510..1020] = 0
+  uint16_t log[256];         // log[0] = 510
+  uint16_t hlog[16 * 256];   // log H[i][j] at [i * n + j]
+  uint16_t pinvlog[256];     // log of 1 / H[piv[j]][j]
+  uint8_t piv[256];          // pivot (first nonzero) row of column j
+  uint32_t hist[256 + 2];    // votes[n], unlocated, bad columns
+};
+
+// One byte column: s_i = byte q of acc[i]. Votes go to the LDS histogram, the two totals to the
+// lane's own counters.
+template <int MT>
+__device__ __forceinline__ void classify(const LocLds& l, uint32_t* hist, const uint32_t (&acc)[MT], int q, int n,
+                                         int p, bool locatable, uint32_t& bad, uint32_t& unl) {
+  uint32_t sp[4] = {0u, 0u, 0u, 0u};  // the syndrome bytes, four rows per word
+  uint32_t nz = 0;
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const uint32_t s = (acc[i] >> (8 * q)) & 0xFFu;
+    sp[i >> 2] |= s << (8 * (i & 3));
+    nz |= uint32_t(s != 0) << i;
+  }
+  if (nz == 0) return;
+  ++bad;
+  if (!locatable) {
+    ++unl;
+    return;
+  }
+  const int k = n - p;
+  if ((nz & (nz - 1)) == 0) {
+    atomicAdd(&hist[k + (__ffs(int(nz)) - 1)], 1u);
+    return;
+  }
+  for (int j = 0; j < k; ++j) {
+    const int r = l.piv[j];
+    const uint32_t w = r < 8 ? (r < 4 ? sp[0] : sp[1]) : (r < 12 ? sp[2] : sp[3]);
+    const uint32_t sr = (w >> (8 * (r & 3))) & 0xFFu;
+    if (sr == 0) continue;  // e would be 0
+    int le = int(l.log[sr]) + int(l.pinvlog[j]);  // log e, e = s_r / H[r][j]
+    if (le >= 255) le -= 255;
+    bool match = true;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      if (i < p) {
+        const uint32_t s = (sp[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+        match = match && uint32_t(l.exp[le + int(l.hlog[i * n + j])]) == s;
+      }
+    }
+    if (match) {
+      atomicAdd(&hist[j], 1u);
+      return;
+    }
+  }
+  ++unl;
 }
 
 template <typename F>

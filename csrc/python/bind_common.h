@@ -134,6 +134,20 @@ inline void bind_common(py::module_& m) {
     r["bytes"] = l.bytes;
     return r;
   }, py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("nblk"));
+  m.def("varlen_scrub_layout", [](int n, int m_pad, int batch, int64_t nblk, int64_t nspan) {
+    const gfrs::VarlenScrubLayout l = gfrs::varlen_scrub_layout(n, m_pad, batch, nblk, nspan);
+    py::dict r;
+    r["in_off"] = l.in_off;
+    r["len_off"] = l.len_off;
+    r["first_off"] = l.first_off;
+    r["span_first_off"] = l.span_first_off;
+    r["mask_first_off"] = l.mask_first_off;
+    r["tab_off"] = l.tab_off;
+    r["blk_off"] = l.blk_off;
+    r["span_off"] = l.span_off;
+    r["bytes"] = l.bytes;
+    return r;
+  }, py::arg("n"), py::arg("m_pad"), py::arg("batch"), py::arg("nblk"), py::arg("nspan"));
   m.def("desc_layout16", [](int k, int m_pad, int batch) {
     const gfrs::DescLayout l = gfrs::desc_layout16(k, m_pad, batch);
     py::dict d;

@@ -259,6 +259,31 @@ PYBIND11_MODULE(_hip, m) {
       py::arg("desc"), py::arg("k"), py::arg("m_pad"), py::arg("batch"), py::arg("npat"), py::arg("nblk"),
       py::arg("bytewise"), py::arg("max_blocks") = 0, py::arg("stream") = 0);
   m.def(
+      "varlen_syndrome",
+      [](uint64_t desc, int n, int m_pad, int ident, int batch, int64_t nblk, int64_t block_bytes, bool bytewise,
+         int max_blocks, uint64_t mask, int64_t nwords, uint64_t stream) {
+        check(launch_gf_varlen_syndrome(reinterpret_cast<const void*>(desc), n, m_pad, ident, batch, nblk, block_bytes,
+                                        bytewise, max_blocks, reinterpret_cast<int32_t*>(mask), nwords,
+                                        as_stream(stream)),
+              "gf_varlen_syndrome");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("m_pad"), py::arg("ident"), py::arg("batch"), py::arg("nblk"),
+      py::arg("block_bytes"), py::arg("bytewise"), py::arg("max_blocks"), py::arg("mask"), py::arg("nwords"),
+      py::arg("stream") = 0);
+  m.def(
+      "varlen_locate",
+      [](uint64_t desc, int n, int p, int batch, int64_t nblk, int64_t nspan, int64_t block_bytes, bool bytewise,
+         int max_blocks, uint64_t mask, uint64_t loc, bool locatable, uint64_t counts, uint64_t stream) {
+        check(launch_gf_varlen_locate(reinterpret_cast<const void*>(desc), n, p, batch, nblk, nspan, block_bytes,
+                                      bytewise, max_blocks, reinterpret_cast<const int32_t*>(mask),
+                                      reinterpret_cast<const uint8_t*>(loc), locatable,
+                                      reinterpret_cast<uint64_t*>(counts), as_stream(stream)),
+              "gf_varlen_locate");
+      },
+      py::arg("desc"), py::arg("n"), py::arg("p"), py::arg("batch"), py::arg("nblk"), py::arg("nspan"),
+      py::arg("block_bytes"), py::arg("bytewise"), py::arg("max_blocks"), py::arg("mask"), py::arg("loc"),
+      py::arg("locatable"), py::arg("counts"), py::arg("stream") = 0);
+  m.def(
       "repair_solve",
       [](uint64_t g, int n, int k, uint64_t surv, uint64_t erased, int npat, int m_pad, uint64_t coeff, uint64_t tab,
          uint64_t status, uint64_t stream) {

@@ -134,7 +134,7 @@ class VarlenCodec:
             GPU, any field on CPU tensors. Its matrices, its solved patterns and its plan cache
             (``rs._plans``) are used, so a new ``rs.G`` drops this codec's plans too.
 
-    Both calls take the stripes in one of two forms:
+    Every call takes the stripes in one of two forms:
 
     * *list form*: a sequence of B items, each an ``[r, C_b]`` uint8 tensor (last stride 1) or a list
       of r 1-D rows of one length ``C_b``;
@@ -214,6 +214,10 @@ class VarlenCodec:
     @staticmethod
     def _repair_key(stripes: _Rows, parity: _Rows | None, raw: np.ndarray) -> tuple:
         return ("vlrep", stripes.key, None if parity is None else parity.key, raw.shape, raw.tobytes())
+
+    @staticmethod
+    def _scrub_key(stripes: _Rows, parity: _Rows | None, block_bytes: int) -> tuple:
+        return ("vlscrub", block_bytes, stripes.key, None if parity is None else parity.key)
 
     def _alloc_parity(self, data: _Rows):
         """Parity in the form of ``data``: packed, a zeroed ``[p, T]`` tensor under the same offsets;
@@ -300,3 +304,88 @@ class VarlenCodec:
             rows = s.rows(int(b)) + ([] if par is None else par.rows(int(b)))
             rs.reconstruct(rows, patterns[int(pat[b])][1])
         return stripes
+
+    # ---- scrub -------------------------------------------------------------------------------
+    def _scrub(self, what: str, stripes, parity, offsets, block_bytes: int, stream, locate: bool):
+        """The call behind :meth:`syndrome_mask` and :meth:`scrub` (``locate``): a cached plan on the
+        GPU, else zeros (p = 0 or no bytes: nothing to check) or the CPU form stripe by stripe."""
+        from ..ops.scrub import MAX_LOCATE_P, check_block_bytes, cpu_scrub
+        from ..ops.varlen import VarlenScrubPlan, make_varlen_report, zero_mask
+
+        rs = self.rs
+        if rs.field != "gf256":
+            raise NotImplementedError(f"{what} is implemented for field='gf256', not {rs.field!r}")
+        s, par = self._parts("stripes", stripes, rs.n if parity is None else rs.k, parity, offsets)
+        block_bytes = check_block_bytes(block_bytes)
+        if s.device.type == "cuda" and rs.p > 0 and s.nstripes > 0:
+            key = self._scrub_key(s, par, block_bytes)
+            plan = rs._plans.get(key)
+            if plan is None and s.lengths.any():  # (a batch of no bytes gets no plan and launches nothing)
+                plan = rs._plans[key] = VarlenScrubPlan(self._ptrs(s, par), s.lengths, rs.H, s.device, block_bytes)
+            if plan is not None:
+                return plan.scrub(stream) if locate else plan.syndrome_mask(stream)  # (scrub refuses p > 16 itself)
+        if locate and rs.p > MAX_LOCATE_P:
+            raise NotImplementedError(f"{what} locates chunks for p <= {MAX_LOCATE_P} (p = {rs.p}); syndrome_mask "
+                                      "works for any p")
+        lengths = s.lengths if s.nstripes else np.zeros(0, dtype=np.int64)
+        mask = zero_mask(lengths, block_bytes, s.device)
+        votes = np.zeros((s.nstripes, rs.n), dtype=np.int64)
+        unlocated, bad = np.zeros(s.nstripes, dtype=np.int64), np.zeros(s.nstripes, dtype=np.int64)
+        if s.device.type != "cuda" and rs.p > 0:
+            h = rs.H
+            for b in np.nonzero(lengths)[0]:
+                b = int(b)
+                rows = s.rows(b) + ([] if par is None else par.rows(b))
+                words, votes[b], unlocated[b], bad[b] = cpu_scrub(h, rows, int(lengths[b]), block_bytes, rs._cpu_gemm,
+                                                                  locate)
+                mask.of(b).copy_(words)
+                mask.stripes[b] = int(np.bitwise_or.reduce(words.numpy()))
+        return make_varlen_report(votes, unlocated, bad, mask) if locate else mask
+
+    def syndrome_mask(self, stripes, parity=None, offsets=None, block_bytes: int = 65536,
+                      stream: torch.cuda.Stream | None = None):
+        """``rs.syndrome_mask`` for every stripe b in ONE launch with no host sync: a
+        :class:`~gpu_rscode_amd.ops.varlen.VarlenMask` whose ``of(b)`` (``blocks[offsets[b]:offsets[b + 1]]``,
+        ``ceil(C_b / block_bytes)`` int32 words on the stripes' device) equals what ``rs.syndrome_mask`` on
+        stripe b alone returns, and whose ``stripes[b]`` is the OR of those words. ``stripes``: B stripes
+        of n rows, natives first, or of k rows with their p parity rows in ``parity``. A stripe of
+        length 0 has no words and a zero stripe word; a batch of nothing but such stripes launches
+        nothing. Any p; no row is written."""
+        return self._scrub("syndrome_mask", stripes, parity, offsets, block_bytes, stream, False)
+
+    def scrub(self, stripes, parity=None, offsets=None, block_bytes: int = 65536,
+              stream: torch.cuda.Stream | None = None):
+        """``rs.scrub`` for every stripe b: on the GPU one launch of each kernel and one sync for the
+        whole batch. Returns a :class:`~gpu_rscode_amd.ops.varlen.VarlenScrubReport`: the fields of
+        ``BatchScrubReport`` with ``mask`` a ``VarlenMask``; ``report[b]`` equals, field for field, what
+        ``rs.scrub`` on stripe b alone returns. p > 16 raises ``NotImplementedError``. No row is written."""
+        return self._scrub("scrub", stripes, parity, offsets, block_bytes, stream, True)
+
+    def heal(self, stripes, parity=None, offsets=None, report=None):
+        """Repair the dirty stripes of the batch in place, each from its own redundancy, by
+        ``rs.heal_batch``'s rule stripe by stripe. Scrubs if no ``report`` is given. A dirty stripe with
+        no unlocated column, 1..p suspects and a recoverable pattern is rewritten as
+        ``rs.reconstruct(stripe_b, erased=suspects_b)`` would, all such stripes in ONE
+        :meth:`reconstruct` call; any other dirty stripe is left byte for byte as it was and listed in
+        ``unhealed``, and nothing is raised for it. If anything was rewritten the batch is scrubbed
+        once more and that second report is returned, else the first; either has ``unhealed`` filled in."""
+        rs = self.rs
+        if rs.field != "gf256":
+            raise NotImplementedError(f"heal is implemented for field='gf256', not {rs.field!r}")
+        if report is None:
+            report = self.scrub(stripes, parity, offsets)
+        unhealed = []
+        erased = np.full((len(report.clean), rs.p), -1, dtype=np.int64)
+        for b in report.dirty:
+            rep = report.report[b]
+            sus = sorted(set(int(e) for e in rep.suspects))
+            if (rep.unlocated > 0 or not sus or len(sus) > rs.p
+                    or not rs.is_recoverable([i for i in range(rs.n) if i not in sus][: rs.k])):
+                unhealed.append(b)  # (nothing is written)
+                continue
+            erased[b, : len(sus)] = sus
+        if (erased >= 0).any():
+            self.reconstruct(stripes, erased, parity, offsets)
+            report = self.scrub(stripes, parity, offsets)
+        report.unhealed = unhealed
+        return report
